@@ -1,7 +1,19 @@
 #!/usr/bin/env python3
 """bench.py -- KF+GRU timesteps/s (BASELINE.json metric) on N MI355X of one node.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
+
+A plain run does what the headline figure needs and nothing else: set up, W warm-up steps, K timed steps, the JSON line (metric,
+value, unit, ms_per_step, ...; modes fused / kf also carry the kernel table and the roofline of the HIP events recorded over the
+timed region itself, which cost no run of their own).  --full adds everything that takes work of its own: the parity block (the
+float64 C oracle over the timed batch), the CPU baselines, the second run under the fitted noise set, the per-kernel event pass and
+roofline of the modes with many short launches, the all-reduce timing and the replica check of --mode train.  --cpu-seconds,
+--parity-samples and --no-second-noise tune those legs and have no effect without --full.
+
+--dump-outputs DIR: after the timed steps, rank 0 writes what the timed path returned in its LAST timed step as DIR/<name>.npy
+(float32 / float64; integer outputs as float64).  An array larger than its share of 48 MB is written as a seeded sample: the elements
+of the flattened array at sorted(default_rng(0).integers(0, size, n)), the same indices in every run of the same arguments.  The
+inputs are seeded, so two builds of the library can be compared output for output.
 
 With N > 1 and no torchrun environment this process starts the N ranks itself (a fresh
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ...` child, BEFORE anything here
@@ -257,6 +269,33 @@ def emit(line):
     else:
         sys.stdout.flush()
         os.write(_JSON_FD, (line + "\n").encode())
+
+
+DUMP_BUDGET_BYTES = 48 * 10 ** 6
+
+
+def dump_outputs(a, rk, arrays):
+    """--dump-outputs: rank 0 writes {name: tensor} of the last timed step as DIR/<name>.npy (module docstring: dtype, sampling)."""
+    if not a.dump_outputs or rk.rank != 0:
+        return
+    import numpy as np
+    import torch
+    arrays = {k: v for k, v in arrays.items() if torch.is_tensor(v)}
+    os.makedirs(a.dump_outputs, exist_ok=True)
+    share = DUMP_BUDGET_BYTES // max(1, len(arrays))
+    for name, t in arrays.items():
+        t = t.detach()
+        if t.dtype != torch.float32:
+            t = t.double()
+        flat = t.reshape(-1)
+        n = share // flat.element_size()
+        if flat.numel() > n:
+            idx = np.sort(np.random.default_rng(0).integers(0, flat.numel(), n))
+            flat = flat[torch.as_tensor(idx, device=flat.device)]
+            arr = flat.cpu().numpy()
+        else:
+            arr = flat.cpu().numpy().reshape(tuple(t.shape))
+        np.save(os.path.join(a.dump_outputs, name + ".npy"), arr)
 
 
 def base_line(a, rk, metric, unit, value, el, dtype, config):
@@ -549,6 +588,14 @@ def oracle_pass(d, x_out, out, model, H, L, Q, R, P0, want, cap_seconds, kf_only
 # ------------------------------------------------------------------------------------------------------------------
 # modes
 # ------------------------------------------------------------------------------------------------------------------
+def train_line(a, rk, B, T, el):
+    return base_line(a, rk, "GRU training windows/sec (gru_train.py step, data parallel)", "windows/s", B * rk.world * a.steps / el,
+                     el, f"f32; weight-gradient GEMMs on bf16x{a.split_bf16}-split operands, f32 accumulate (opt-in)" if a.split_bf16 else "f32",
+                     {"workload": "gru_train.py step RNN(188,128,4,24), Adam lr 1e-4, windows of 10", "batch_per_gpu": B,
+                      "seq_len": T, "global_batch": B * rk.world,
+                      "parallelism": f"dp{rk.world}, one flat fp32 bucket all-reduce", "baseline_config": "BASELINE.json configs[3]"})
+
+
 def bench_train(a, rk):
     """BASELINE configs[3]: data-parallel gru_train.py step, RNN(188,128,4,24), 8192 windows of 10 steps per GPU, Adam 1e-4,
     one flat 1.69 MB fp32 gradient bucket all-reduced per step.  A 'step' here is one optimisation step."""
@@ -567,6 +614,13 @@ def bench_train(a, rk):
     g = torch.Generator(device=dev); g.manual_seed(100 + rk.rank)
     x = torch.rand(B, T, I, device=dev, generator=g); y = torch.rand(B, C // 2, device=dev, generator=g)
     el, loss, _ = timed_region(rk, a.warmup, a.steps, lambda: tr.step(x, y))
+    # what a caller of step() holds afterwards: the loss it returned and the updated weights (the flat parameter vector)
+    dump_outputs(a, rk, {"loss": loss, "weights": tr.bucket.w})
+    if not a.full:
+        info = rk.report()
+        if rk.rank == 0:
+            emit(json.dumps({**train_line(a, rk, B, T, el), "final_loss": float(loss.item()), "grad_bucket_bytes": int(tr.bucket.g.numel() * 4), **info}))
+        return
     kernels = events_pass(tr.eng, max(2, min(a.steps, 5)), lambda: tr.step(x, y))
     ar_us = None
     if rk.dist:
@@ -595,10 +649,7 @@ def bench_train(a, rk):
         dk = kernels[dom]
         fl_launch = phase_flops[dom] / dk["launches_per_step"]
         ach = fl_launch / (dk["ms_per_launch"] * 1e-3) / 1e12
-        out = base_line(a, rk, "GRU training windows/sec (gru_train.py step, data parallel)", "windows/s", B * rk.world * a.steps / el,
-                        el, f"f32; weight-gradient GEMMs on bf16x{a.split_bf16}-split operands, f32 accumulate (opt-in)" if a.split_bf16 else "f32", {"workload": "gru_train.py step RNN(188,128,4,24), Adam lr 1e-4, windows of 10", "batch_per_gpu": B,
-                                    "seq_len": T, "global_batch": B * rk.world,
-                                    "parallelism": f"dp{rk.world}, one flat fp32 bucket all-reduce", "baseline_config": "BASELINE.json configs[3]"})
+        out = train_line(a, rk, B, T, el)
         tot = fl_fwd + fl_sweep + fl_dw
         out["roofline"] = {"kernel": dk["kernel"] + " (v_mfma_f32_32x32x2_f32)", "bound": "mfma", "achieved": ach, "peak": MFMA_F32_PEAK_TF,
                            "unit": "TFLOP/s", "frac": ach / MFMA_F32_PEAK_TF, "traffic": None, "traffic_source": "not collected for this mode", "avg_launch_ms": dk["ms_per_launch"],
@@ -641,8 +692,9 @@ def bench_full(a, rk):
         lat = vit.forward_encoder(frames).reshape(B, T, 128)
         x, P = d["x0"].clone(), d["P0"].clone()
         return eng.fused_run(d["p"], d["f"], d["dp"], d["imu"], contact, d["accel"], minmax, x, P, latent=eng.pack(lat))
-    el, _, _ = timed_region(rk, a.warmup, a.steps, one)
-    kernels = events_pass(eng, max(2, min(a.steps, 5)), one)
+    el, last, _ = timed_region(rk, a.warmup, a.steps, one)
+    dump_outputs(a, rk, last)
+    kernels = events_pass(eng, max(2, min(a.steps, 5)), one) if a.full else {}
     info = rk.report()
     if rk.rank == 0:
         N = B * T
@@ -666,10 +718,11 @@ def bench_full(a, rk):
                                "frac": ach / MFMA_F32_PEAK_TF, "traffic": None, "traffic_source": "not collected for this mode", "avg_launch_ms": dk["ms_per_launch"],
                                "algorithmic_flops_per_launch": fl_launch, "phase": dom,
                                "note": "average over the launches of the phase (the projections differ in shape)"}
-        out["kernels"] = kernels
-        out["kernel_events"] = "HIP events in a second, untimed pass of the same step"
+        if a.full:
+            out["kernels"] = kernels
+            out["kernel_events"] = "HIP events in a second, untimed pass of the same step"
         out.update(info)
-        out["cpu_baseline"] = cpu_baseline_full(a.cpu_seconds) if (a.cpu_seconds > 0 and rk.world == 1) else None
+        out["cpu_baseline"] = cpu_baseline_full(a.cpu_seconds) if (a.full and a.cpu_seconds > 0 and rk.world == 1) else None
         emit(json.dumps(out))
 
 
@@ -693,7 +746,8 @@ def bench_mpc(a, rk):
         x, P = d["x0"].clone(), d["P0"].clone()
         return eng.kf_mpc_run(d["p"], d["dp"], d["imu"], contact, ref, x, P, want_iters=True)
     el, last, _ = timed_region(rk, a.warmup, a.steps, one)
-    kernels = events_pass(eng, 1, one)
+    dump_outputs(a, rk, last)
+    kernels = events_pass(eng, 1, one) if a.full else {}
     info = rk.report()
     if rk.rank == 0:
         it = last["iters"].float()
@@ -744,7 +798,9 @@ def bench_mpc(a, rk):
         out.update(qp_iterations_mean=float(it.mean()), qp_iterations_max=int(it.max()),
                    status_nonzero_trajectories=int(eng.failed(last["status"]).sum()),
                    trunc_edge_trajectories=int(eng.trunc_edge(last["status"]).sum()), kernels=kernels, **info)
-        out["cpu_baseline"] = cpu_baseline_mpc(min(a.cpu_seconds, 20.0)) if (a.cpu_seconds > 0 and rk.world == 1) else None
+        if not a.full:                  # no event pass was run: the line carries neither its kernel table nor the roofline built on it
+            del out["roofline"], out["kernels"]
+        out["cpu_baseline"] = cpu_baseline_mpc(min(a.cpu_seconds, 20.0)) if (a.full and a.cpu_seconds > 0 and rk.world == 1) else None
         emit(json.dumps(out))
 
 
@@ -768,8 +824,9 @@ def bench_windows(a, rk):
         one = lambda: predict_windows(model, w, mn, mx)
     else:
         one = lambda: predict_rows(model, rows, T, mn, mx)
-    el, _, _ = timed_region(rk, a.warmup, a.steps, one)
-    kernels = events_pass(model._engine, max(2, min(a.steps, 5)), one)
+    el, last, _ = timed_region(rk, a.warmup, a.steps, one)
+    dump_outputs(a, rk, dict(zip(("pred", "band_above", "band_below"), last)))
+    kernels = events_pass(model._engine, max(2, min(a.steps, 5)), one) if a.full else {}
     info = rk.report()
     if rk.rank == 0:
         out = base_line(a, rk, "sliding-window GRU outputs/sec (gru_test.py inference mode, window 10 from h0=0)", "windows/s",
@@ -791,9 +848,10 @@ def bench_windows(a, rk):
                                "traffic": None, "traffic_source": "not collected for this mode", "avg_launch_ms": dk["ms_per_launch"],
                                "algorithmic_flops_per_pass": fl, "flops_of_the_materialised_form": fl_full,
                                "note": "achieved = the form's own (reduced) flop count over the summed device time of its GRU launches"}
-        out["kernels"] = kernels
+        if a.full:
+            out["kernels"] = kernels
         out.update(info)
-        if a.cpu_seconds > 0 and rk.world == 1:
+        if a.full and a.cpu_seconds > 0 and rk.world == 1:
             cores = usable_cores(); torch.set_num_threads(cores)
             ref = torch.nn.GRU(I, H, L, batch_first=True); fc = torch.nn.Linear(H, 24)
             xb = torch.rand(2048, T, I)
@@ -878,6 +936,7 @@ def bench_hot_path(a, rk):
         return el, r, kernels, Q, R
 
     el, r, kernels, Q, R = run_set(a.noise, a.warmup, a.steps)
+    dump_outputs(a, rk, {**r, "x_final": x, "P_final": P})           # x, P: the filter state the call advanced in place
     bad = int(eng.failed(r["status"]).sum().item())           # bits 0-3; bit 4 is informational and counted on its own
     edge = int(eng.trunc_edge(r["status"]).sum().item())
     info = rk.report()
@@ -985,7 +1044,7 @@ def bench_hot_path(a, rk):
     # region; the oracle's seconds double as the all-cores cpu_baseline (one run serves both)
     all_cores = None
     cap = max(4.0 * a.cpu_seconds, 60.0)
-    if a.parity_samples != 0:
+    if a.full and a.parity_samples != 0:
         want = B if a.parity_samples < 0 else min(a.parity_samples, B)
         if rk.world > 1 and a.parity_samples < 0:
             want = min(B, 8192)            # N ranks share the host cores (torchrun pins OMP_NUM_THREADS): a sample of rank 0's shard
@@ -995,7 +1054,7 @@ def bench_hot_path(a, rk):
         if a.split_bf16:
             out["parity"]["gru_bar"] = 1e-5
             out["parity"]["note"] = "opt-in split-bf16 gate GEMM: the GRU bar stays 1e-5, the fused chain < 1e-4"
-    if a.second_noise and a.noise == "default" and rk.world == 1 and not a.split_bf16:
+    if a.full and a.second_noise and a.noise == "default" and rk.world == 1 and not a.split_bf16:
         # "second run with Q_R.pkl values" -- the reference's fitted Q / R (cond(S) ~ 1e6) on the same inputs
         el2, r2, k2, Q2, R2 = run_set("fitted", 1, 3)
         sec = {"noise": NOISE_NOTE["fitted"], "steps": 3, "ms_per_step": el2 / 3 * 1e3, "value": steps_per_pass * rk.world * 3 / el2,
@@ -1005,7 +1064,7 @@ def bench_hot_path(a, rk):
             want2 = B if a.parity_samples < 0 else min(a.parity_samples, B)
             sec["parity"], _ = oracle_pass(d, r2["x_out"], r2.get("out"), model, H, L, Q2, R2, Q2, want2, cap, kf_only=not fused, latent=latent)
         out["second_noise_set"] = sec
-    if a.cpu_seconds > 0 and rk.world == 1:
+    if a.full and a.cpu_seconds > 0 and rk.world == 1:
         out["cpu_baseline"] = cpu_baseline(H, L, a.cpu_seconds, kf_only=not fused, all_cores=all_cores if a.latent == 0 else None)
         if a.latent:
             out["cpu_baseline"]["note"] = "sampled on the 60-wide input (no latent stream)"
@@ -1047,13 +1106,18 @@ def main(argv=None):
     ap.add_argument("--hidden", type=int, default=64)
     ap.add_argument("--layers", type=int, default=1)
     ap.add_argument("--latent", type=int, default=0, help="width of a latent stream appended to the 60 Kalman features (128: the reference's 188-wide GRU input)")
-    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="CPU baseline sample budget (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline figure: parity against the float64 oracle, CPU baselines, the second noise set, the per-kernel "
+                         "event pass and roofline of the modes that need a pass of their own, all-reduce timing and replica check (train)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (float32 / float64; large arrays as a seeded sample)")
+    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="--full: CPU baseline sample budget (0 = skip)")
     ap.add_argument("--parity-samples", type=int, default=-1,
-                    help="trajectories of the timed batch checked against the oracle over all their timesteps (-1 = the whole batch, 0 = skip)")
+                    help="--full: trajectories of the timed batch checked against the oracle over all their timesteps (-1 = the whole batch, 0 = skip)")
     ap.add_argument("--noise", default="default", choices=["default", "fitted"],
                     help="Q / R set: settings.py defaults, or the reference's fitted Q_R.pkl values with R[0:3] = 1e-4")
     ap.add_argument("--no-second-noise", dest="second_noise", action="store_false",
-                    help="skip the short second run under the fitted noise set that the default line carries as second_noise_set")
+                    help="--full: skip the short second run under the fitted noise set that the default line carries as second_noise_set")
     ap.add_argument("--hostile", action="store_true",
                     help="inputs that leave the fast branches: 0-4 stance legs per step, yaw unwrapping past +-pi, wide roll / pitch")
     ap.add_argument("--split-bf16", type=int, nargs="?", const=3, default=0, choices=[0, 2, 3],

@@ -115,3 +115,28 @@ def test_traffic_figure_is_served_only_with_matching_provenance(tmp_path, monkey
     tj.write_text(json.dumps(entry))
     assert bench.load_traffic("fused_kf_gru_kernel_v2", True)[0] is None
     assert bench.load_traffic("kf_run_sym_kernel", True)[0] is None   # no entry at all
+
+
+def test_dump_outputs_writes_float_arrays_and_a_seeded_sample_of_a_large_one(tmp_path, monkeypatch):
+    """--dump-outputs: every tensor of the last step as <name>.npy in float32 / float64 (integers as float64, non-tensors left out);
+    an array over its share of the byte budget is a sample of its flattened elements at seeded indices, the same in every run;
+    only rank 0 writes."""
+    import argparse
+    import numpy as np
+    import torch
+    import bench
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 3 * 400)
+    big = torch.arange(1000, dtype=torch.float32).reshape(10, 100)
+    arrays = {"big": big, "small": torch.ones(2, 3, dtype=torch.float64), "status": torch.tensor([0, 16], dtype=torch.int32), "none": None}
+    rk0, rk1 = argparse.Namespace(rank=0), argparse.Namespace(rank=1)
+    bench.dump_outputs(argparse.Namespace(dump_outputs=None), rk0, arrays)                     # not asked for: nothing happens
+    bench.dump_outputs(argparse.Namespace(dump_outputs=str(tmp_path / "r1")), rk1, arrays)
+    assert not (tmp_path / "r1").exists()
+    for d in ("a", "b"):
+        bench.dump_outputs(argparse.Namespace(dump_outputs=str(tmp_path / d)), rk0, arrays)
+    assert sorted(os.listdir(tmp_path / "a")) == ["big.npy", "small.npy", "status.npy"]
+    small, status, s = (np.load(tmp_path / "a" / n) for n in ("small.npy", "status.npy", "big.npy"))
+    assert small.dtype == np.float64 and small.shape == (2, 3) and status.dtype == np.float64 and status.tolist() == [0.0, 16.0]
+    idx = np.sort(np.random.default_rng(0).integers(0, 1000, 100))
+    assert s.dtype == np.float32 and s.nbytes == 400 and np.array_equal(s, idx.astype(np.float32))     # big[i] == i
+    assert np.array_equal(s, np.load(tmp_path / "b" / "big.npy"))

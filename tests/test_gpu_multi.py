@@ -38,7 +38,7 @@ def test_one_gpu_full_batch_equals_two_gpus_half_batches():
 
 @pytest.mark.parametrize("mode", ["fused", "train"])
 def test_bench_gpus_2_launches_itself(mode):
-    args = ["--gpus", "2", "--steps", "2", "--warmup", "1", "--cpu-seconds", "0", "--mode", mode]
+    args = ["--full", "--gpus", "2", "--steps", "2", "--warmup", "1", "--cpu-seconds", "0", "--mode", mode]
     if mode == "fused":
         args += ["--batch", "8192", "--seq", "20"]
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args, capture_output=True, text=True, timeout=900, env=ENV)

@@ -94,7 +94,7 @@ def test_bench_scaling_strong_two_ranks_equal_the_one_rank_checksum():
     the global checksums agree to fp32 noise (SURVEY 8(e) determinism check), `value` counts the global batch once."""
     outs = {}
     for n in (1, 2):
-        args = ["--gpus", str(n), "--scaling", "strong", "--batch", "16384", "--seq", "20", "--steps", "2", "--warmup", "1", "--cpu-seconds", "0",
+        args = ["--full", "--gpus", str(n), "--scaling", "strong", "--batch", "16384", "--seq", "20", "--steps", "2", "--warmup", "1", "--cpu-seconds", "0",
                 "--parity-samples", "128", "--no-second-noise"] + (["--share-gpu"] if n > 1 else [])
         r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args, capture_output=True, text=True, timeout=900, env=ENV)
         assert r.returncode == 0, r.stderr[-3000:]
@@ -112,7 +112,7 @@ def test_bench_scaling_strong_two_ranks_equal_the_one_rank_checksum():
 
 @pytest.mark.parametrize("mode", ["fused", "train"])
 def test_bench_gpus_2_share_gpu(mode):
-    args = ["--gpus", "2", "--share-gpu", "--steps", "2", "--warmup", "1", "--cpu-seconds", "0", "--mode", mode]
+    args = ["--full", "--gpus", "2", "--share-gpu", "--steps", "2", "--warmup", "1", "--cpu-seconds", "0", "--mode", mode]
     if mode == "fused":
         args += ["--batch", "8192", "--seq", "20"]
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args, capture_output=True, text=True, timeout=900, env=ENV)

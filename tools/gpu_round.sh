@@ -4,7 +4,7 @@ TAG=${1:-r01}
 OUT=$GRAFT_REPO_ROOT/gpurun_out
 mkdir -p $OUT
 python -m pytest tests -m gpu -x -q 2>&1 | tail -15 | tee $OUT/pytest_gpu_$TAG.log
-python bench.py --steps 10 --warmup 2 2> $OUT/bench_$TAG.err | tee $OUT/bench_$TAG.json
+python bench.py --full --steps 10 --warmup 2 2> $OUT/bench_$TAG.err | tee $OUT/bench_$TAG.json
 tail -3 $OUT/bench_$TAG.err
 R=$GRAFT_REPO_ROOT
 cd /tmp && export TMPDIR=/tmp

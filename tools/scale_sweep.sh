@@ -13,14 +13,14 @@ for mode in fused train; do
   for n in 1 2 4 8; do
     [ $n -le $MAXG ] || continue
     extra=""; [ $mode = train ] && extra="--mode train"
-    timeout 900 python3 bench.py --gpus $n $extra --steps 10 --warmup 3 --cpu-seconds 0 --parity-samples 0 --no-second-noise \
+    timeout 900 python3 bench.py --full --gpus $n $extra --steps 10 --warmup 3 --cpu-seconds 0 --parity-samples 0 --no-second-noise \
         > $O/${mode}_n$n.json 2> $O/${mode}_n$n.err || echo "bench $mode n=$n failed (rc $?)" >&2
   done
 done
 # the latency-bound 1.69 MB gradient bucket under each RCCL protocol, at the largest world size
 for proto in LL LL128 Simple; do
   n=$MAXG; [ $n -ge 2 ] || continue
-  timeout 900 python3 bench.py --gpus $n --mode train --rccl-proto $proto --steps 10 --warmup 3 --cpu-seconds 0 \
+  timeout 900 python3 bench.py --full --gpus $n --mode train --rccl-proto $proto --steps 10 --warmup 3 --cpu-seconds 0 \
       > $O/train_n${n}_$proto.json 2> $O/train_n${n}_$proto.err || echo "bench train n=$n proto=$proto failed (rc $?)" >&2
 done
 python3 - "$O" <<'PY'
