@@ -336,6 +336,26 @@ size_t os_vit_param_count(const os_vit_dims *d);
 int os_vit_load(os_ctx *ctx, const os_vit_dims *d, const float *w_flat);
 int os_vit_encode(os_ctx *ctx, int32_t N, const float *images, float *latent, void *stream);
 
+/* Decoder half of the same class (transformer/transformer_model.py:137-175: forward_decoder, forward_loss, unpatchify).
+ * `dec` carries img_size, patch_size, in_chans, embed_dim = decoder_embed_dim, depth = decoder_depth, num_heads =
+ * decoder_num_heads, mlp_hidden; latent_dim is the encoder's embed_dim.  With Dd = decoder_embed_dim, L = 1 + (img/patch)^2 and
+ * PP = patch_size^2 * in_chans the flat weight layout (device floats) is: decoder_embed.weight [Dd][latent_dim], .bias [Dd],
+ * decoder_noise_token [Dd], decoder_pos_embed [L][Dd]; per decoder block the twelve tensors in the encoder's per-block order
+ * (above); decoder_norm.weight, .bias [Dd]; decoder_pred.weight [PP][Dd], .bias [PP].
+ * os_vit_load_decoder accepts os_vit_load's dimension limits with PP a multiple of 32 and latent_dim <= 1024 (-4 with a message
+ * otherwise), does not need os_vit_load, references w_flat (caller-owned, must outlive the calls below), re-packs the matrices
+ * on the null stream and waits for that; its state is released with the context.
+ * os_vit_decode: latent [N][latent_dim] -> any of pred [N][L-1][PP] (the reference's forward_decoder), recon [N][img][img]
+ * (= unpatchify(pred), the same floats) and loss (one device float = mean((pred - patchify(images))^2), needs images
+ * [N][img][img]); a null output is not produced.  os_vit_recon_loss: the same loss for a pred already in memory
+ * (forward_loss).  The loss is summed in float64 in a fixed order: the same inputs give the same bits.  Both are stream-ordered:
+ * no host synchronisation, and no allocation after the first call at a given N. */
+size_t os_vit_decoder_param_count(const os_vit_dims *dec, int32_t latent_dim);
+int os_vit_load_decoder(os_ctx *ctx, const os_vit_dims *dec, int32_t latent_dim, const float *w_flat);
+int os_vit_decode(os_ctx *ctx, int32_t N, const float *latent, const float *images, float *pred, float *recon, float *loss,
+                  void *stream);
+int os_vit_recon_loss(os_ctx *ctx, int32_t N, const float *images, const float *pred, float *loss, void *stream);
+
 /* ---- Convex-MPC ground-reaction forces ("next" row f.2): the QP the reference solves with casadi + qpOASES inside
  * predict_mpc (misc/force_controller.py:70-162 builds it, kalman_filter/kalman_filter.py:141-152 fills the parameters
  * and takes column 0 of the solution).  N = 5 horizon steps x 12 forces; per trajectory:

@@ -40,6 +40,7 @@ EXPORTS = [
     "os_profile_kernel_name", "os_build_id", "os_kf_step", "os_gru_load_keyed", "os_pack_stream_rows", "os_gru_backward_mark",
     "os_gru_forward_windows", "os_gru_bands", "os_gru_set_stack", "os_gru_set_split_bf16",
     "os_gru_get_stack", "os_fused_set_tile", "os_stack_check", "os_kf_step_mpc",
+    "os_vit_decoder_param_count", "os_vit_load_decoder", "os_vit_decode", "os_vit_recon_loss",
 ]
 
 
@@ -135,6 +136,13 @@ def load():
     lib.os_vit_encode.argtypes = [vp, i32, f32p, f32p, vp]
     lib.os_vit_load.restype = C.c_int
     lib.os_vit_encode.restype = C.c_int
+    lib.os_vit_decoder_param_count.argtypes = [C.POINTER(OsVitDims), i32]
+    lib.os_vit_decoder_param_count.restype = C.c_size_t
+    lib.os_vit_load_decoder.argtypes = [vp, C.POINTER(OsVitDims), i32, f32p]
+    lib.os_vit_decode.argtypes = [vp, i32, f32p, f32p, f32p, f32p, f32p, vp]
+    lib.os_vit_recon_loss.argtypes = [vp, i32, f32p, f32p, f32p, vp]
+    for n in ("os_vit_load_decoder", "os_vit_decode", "os_vit_recon_loss"):
+        getattr(lib, n).restype = C.c_int
     lib.os_mpc_set_weights.argtypes = [vp, C.POINTER(C.c_double), C.c_double, C.c_double, C.c_double]
     lib.os_mpc_solve.argtypes = [vp, i32, f32p, f32p, f32p, vp, f32p, f32p, vp, vp, i32, vp]
     lib.os_kf_mpc_run.argtypes = [vp, i32, i32, f32p, f32p, f32p, vp, f32p, f32p, f32p, f32p, f32p, f32p, f32p, f32p, vp, vp, u32, vp]

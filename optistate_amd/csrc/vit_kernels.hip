@@ -10,16 +10,11 @@
 // prologue / epilogues (vit_gemm_kernel: patch extraction while staging, bias, bias + GELU, bias + residual, patch bias +
 // position table); LayerNorm, per-(image, head) attention on the matrix cores, and the final LayerNorm + sigmoid of the cls
 // token are separate kernels.  No vendor BLAS.
-#include "launch.hpp"
+#include "vit_host.hpp"
 
 #include <math.h>
 
 namespace osv {
-
-struct VitDims { int img, patch, dim, depth, heads, mlp; };
-
-__host__ __device__ inline int grid_of(const VitDims &d) { return d.img / d.patch; }
-__host__ __device__ inline int ntok(const VitDims &d) { return grid_of(d) * grid_of(d) + 1; }
 
 // LayerNorm over rows of D (D <= 256, one wave per row, eps 1e-5)
 __global__ void layernorm_kernel(size_t M, int D, const float *X, const float *w, const float *b, float *Y, size_t x_stride)
@@ -1025,14 +1020,6 @@ __global__ void cls_head_kernel(int N, int L, int D, const float *X, const float
 
 using namespace osv;
 
-struct os_vit_state {
-    VitDims d;
-    const float *w;          // caller-owned flat weights
-    float *wp; size_t wp_floats;       // every projection matrix re-packed into B-fragment order (vit_pack_w_kernel)
-    float *buf; size_t buf_floats;
-    bool att_attr_set, mlp_attr_set;
-};
-
 static size_t vit_param_count(const VitDims &d)
 {
     const size_t D = d.dim, PP = (size_t)d.patch * d.patch, L = ntok(d), Mh = d.mlp;
@@ -1045,6 +1032,7 @@ void os_vit_destroy(os_ctx *ctx)
 {
     os_vit_state *v = (os_vit_state *)ctx->vit;
     if (!v) return;
+    os_vit_decoder_destroy(v);
     if (v->buf) (void)hipFree(v->buf);
     if (v->wp) (void)hipFree(v->wp);
     free(v);
@@ -1060,90 +1048,30 @@ static void launch_gemm(os_ctx *ctx, const GemmArgs &g, hipStream_t s, const cha
     os_prof_end(ctx, slot, s);
 }
 
-extern "C" {
-
-size_t os_vit_param_count(const os_vit_dims *d)
+os_vit_state *os_vit_state_get(os_ctx *ctx)
 {
-    VitDims v{d->img_size, d->patch_size, d->embed_dim, d->depth, d->num_heads, d->mlp_hidden};
-    return vit_param_count(v);
-}
-
-int os_vit_load(os_ctx *ctx, const os_vit_dims *d, const float *w_flat)
-{
-    OS_CHECK_CTX(ctx);
-    if (!d || !w_flat) return os_fail(ctx, -2, "os_vit_load: null pointer");
-    if (d->embed_dim > 256 || d->embed_dim % d->num_heads || d->img_size % d->patch_size || d->in_chans != 1)
-        return os_fail(ctx, -4, "os_vit_load: unsupported dimensions (embed_dim <= 256, one input channel)");
-    const int hd = d->embed_dim / d->num_heads;
-    if (hd != 32 && hd != 64) return os_fail(ctx, -4, "os_vit_load: head dimension must be 32 or 64");
-    if (d->embed_dim % 128 || d->mlp_hidden % 128 || (d->patch_size * d->patch_size) % 128 || d->patch_size % 4)
-        return os_fail(ctx, -4, "os_vit_load: embed_dim, mlp_hidden and patch_size^2 must be multiples of 128 (GEMM k-chunk)");
-    OS_HIP(ctx, hipSetDevice(ctx->device));
     os_vit_state *v = (os_vit_state *)ctx->vit;
     if (!v) {
         v = (os_vit_state *)calloc(1, sizeof(os_vit_state));
-        if (!v) return os_fail(ctx, -13, "os_vit_load: out of memory");
+        if (!v) { os_fail(ctx, -13, "os_vit: out of memory"); return nullptr; }
         ctx->vit = v;
     }
-    v->d = VitDims{d->img_size, d->patch_size, d->embed_dim, d->depth, d->num_heads, d->mlp_hidden};
-    v->w = w_flat;
-    // re-pack the projection matrices once (inference weights are static): [patch | per block: qkv, proj, fc1, fc2]
-    const size_t D = d->embed_dim, PP = (size_t)d->patch_size * d->patch_size, L = ntok(v->d), Mh = d->mlp_hidden;
-    const size_t total = D * PP + (size_t)d->depth * (3 * D * D + D * D + 2 * Mh * D);
-    if (os_ensure_scratch(ctx, &v->wp, &v->wp_floats, total)) return -10;
-    auto pack = [&](int N, int K, const float *W, float *dst) {
-        hipLaunchKernelGGL(vit_pack_w_kernel, dim3(256), dim3(256), 0, 0, N, K, W, dst);
-    };
-    const float *w = w_flat;
-    float *o = v->wp;
-    pack((int)D, (int)PP, w, o); o += D * PP; w += D * PP + D + D + L * D;
-    for (int blk = 0; blk < d->depth; blk++) {
-        w += 2 * D;
-        pack((int)(3 * D), (int)D, w, o); o += 3 * D * D; w += 3 * D * D + 3 * D;
-        pack((int)D, (int)D, w, o); o += D * D; w += D * D + D;
-        w += 2 * D;
-        pack((int)Mh, (int)D, w, o); o += Mh * D; w += Mh * D + Mh;
-        pack((int)D, (int)Mh, w, o); o += D * Mh; w += D * Mh + D;
-    }
-    OS_HIP(ctx, hipGetLastError());
-    OS_HIP(ctx, hipStreamSynchronize(0));
-    return 0;
+    return v;
 }
 
-int os_vit_encode(os_ctx *ctx, int32_t N, const float *images, float *latent, void *stream)
+void os_vit_pack_w(int N, int K, const float *W, float *dst, hipStream_t s)
 {
-    OS_CHECK_CTX(ctx);
-    os_vit_state *v = (os_vit_state *)ctx->vit;
-    if (!v || !v->w) return os_fail(ctx, -5, "os_vit_encode: call os_vit_load first");
-    if (N <= 0 || !images || !latent) return os_fail(ctx, -2, "os_vit_encode: bad argument");
-    OS_HIP(ctx, hipSetDevice(ctx->device));
-    hipStream_t s = (hipStream_t)stream;
-    const VitDims &d = v->d;
-    const int D = d.dim, L = ntok(d), G = grid_of(d), PP = d.patch * d.patch, Mh = d.mlp, hd = D / d.heads;
-    const size_t M = (size_t)N * L, Mp = (size_t)N * G * G;
-    // scratch: X [M][D] (token matrix) | Y [M][D] | big [M][max(3D, mlp)]
-    const size_t bigw = (size_t)(3 * D > Mh ? 3 * D : Mh);
-    const size_t need = M * D * 2 + M * bigw;
-    if (os_ensure_scratch(ctx, &v->buf, &v->buf_floats, need)) return -10;
-    float *X = v->buf, *Y = X + M * D, *big = Y + M * D;
-    const float *w = v->w;
-    const float *wp = v->wp;
-    const float *patch_b = w + (size_t)D * PP, *cls = patch_b + D, *pos = cls + D;
-    w = pos + (size_t)L * D;
+    hipLaunchKernelGGL(vit_pack_w_kernel, dim3(256), dim3(256), 0, s, N, K, W, dst);
+}
+
+// the block loop of encoder and decoder (contract in vit_host.hpp)
+int os_vit_run_blocks(os_ctx *ctx, os_vit_state *v, const VitDims &d, const float *w, const float *wp, float *X, float *Y,
+                      float *big, int N, hipStream_t s, const float **w_end)
+{
+    const int D = d.dim, L = ntok(d), Mh = d.mlp, hd = D / d.heads;
+    const size_t M = (size_t)N * L;
     GemmArgs g;
-    g.img = images; g.img_size = d.img; g.grid = G; g.pos = pos; g.L = L; g.A = nullptr; g.lda = 0;
-    // patch embedding straight from the images into the token matrix (+ patch bias + position table); cls rows beside it
-    g.M = Mp; g.N = D; g.K = PP; g.Wp = wp; g.bias = patch_b; g.C = X;
-    g.patch = d.patch;
-    launch_gemm<1, 3>(ctx, g, s, "vit_gemm_kernel<patch,+pos>");
-    wp += (size_t)D * PP;
-    {
-        const int slot = os_prof_begin(ctx, OS_PHASE_VIT_MISC, s, "cls_row_kernel");
-        hipLaunchKernelGGL(cls_row_kernel, dim3((N * D + 255) / 256), dim3(256), 0, s, N, L, D, cls, pos, X);
-        os_prof_end(ctx, slot, s);
-    }
-    OS_HIP(ctx, hipGetLastError());
-    g.M = M;
+    g.img = nullptr; g.img_size = 0; g.grid = 0; g.patch = 0; g.pos = nullptr; g.L = L; g.M = M;
     for (int blk = 0; blk < d.depth; blk++) {
         const float *ln1w = w; w += D; const float *ln1b = w; w += D;
         w += (size_t)3 * D * D; const float *qkvb = w; w += 3 * D;
@@ -1178,7 +1106,7 @@ int os_vit_encode(os_ctx *ctx, int32_t N, const float *images, float *latent, vo
                 const size_t dlds = (size_t)2 * L * (36 + 32) * sizeof(float);
                 hipLaunchKernelGGL(attention_mfma_dma_kernel<7>, dim3(nitems < cus ? nitems : cus), dim3(512), dlds, s, L, D, d.heads, nitems, big, Y);
             } else
-            hipLaunchKernelGGL(attention_mfma_kernel<7>, dim3(N * d.heads), dim3(512), mlds, s, L, D, d.heads, big, qkvb, Y);
+                hipLaunchKernelGGL(attention_mfma_kernel<7>, dim3(N * d.heads), dim3(512), mlds, s, L, D, d.heads, big, qkvb, Y);
         } else if (hd == 32) hipLaunchKernelGGL(attention_kernel<32>, dim3(N * d.heads), dim3(256), alds, s, L, D, d.heads, big, qkvb, Y);
         else hipLaunchKernelGGL(attention_kernel<64>, dim3(N * d.heads), dim3(256), alds, s, L, D, d.heads, big, qkvb, Y);
         os_prof_end(ctx, slot, s);
@@ -1244,6 +1172,90 @@ int os_vit_encode(os_ctx *ctx, int32_t N, const float *images, float *latent, vo
         }
         OS_HIP(ctx, hipGetLastError());
     }
+    *w_end = w;
+    return 0;
+}
+
+extern "C" {
+
+size_t os_vit_param_count(const os_vit_dims *d)
+{
+    VitDims v{d->img_size, d->patch_size, d->embed_dim, d->depth, d->num_heads, d->mlp_hidden};
+    return vit_param_count(v);
+}
+
+int os_vit_load(os_ctx *ctx, const os_vit_dims *d, const float *w_flat)
+{
+    OS_CHECK_CTX(ctx);
+    if (!d || !w_flat) return os_fail(ctx, -2, "os_vit_load: null pointer");
+    if (d->embed_dim > 256 || d->embed_dim % d->num_heads || d->img_size % d->patch_size || d->in_chans != 1)
+        return os_fail(ctx, -4, "os_vit_load: unsupported dimensions (embed_dim <= 256, one input channel)");
+    const int hd = d->embed_dim / d->num_heads;
+    if (hd != 32 && hd != 64) return os_fail(ctx, -4, "os_vit_load: head dimension must be 32 or 64");
+    if (d->embed_dim % 128 || d->mlp_hidden % 128 || (d->patch_size * d->patch_size) % 128 || d->patch_size % 4)
+        return os_fail(ctx, -4, "os_vit_load: embed_dim, mlp_hidden and patch_size^2 must be multiples of 128 (GEMM k-chunk)");
+    OS_HIP(ctx, hipSetDevice(ctx->device));
+    os_vit_state *v = os_vit_state_get(ctx);
+    if (!v) return -13;
+    v->d = VitDims{d->img_size, d->patch_size, d->embed_dim, d->depth, d->num_heads, d->mlp_hidden};
+    v->w = w_flat;
+    // re-pack the projection matrices once (inference weights are static): [patch | per block: qkv, proj, fc1, fc2]
+    const size_t D = d->embed_dim, PP = (size_t)d->patch_size * d->patch_size, L = ntok(v->d), Mh = d->mlp_hidden;
+    const size_t total = D * PP + (size_t)d->depth * (3 * D * D + D * D + 2 * Mh * D);
+    if (os_ensure_scratch(ctx, &v->wp, &v->wp_floats, total)) return -10;
+    auto pack = [&](int N, int K, const float *W, float *dst) {
+        hipLaunchKernelGGL(vit_pack_w_kernel, dim3(256), dim3(256), 0, 0, N, K, W, dst);
+    };
+    const float *w = w_flat;
+    float *o = v->wp;
+    pack((int)D, (int)PP, w, o); o += D * PP; w += D * PP + D + D + L * D;
+    for (int blk = 0; blk < d->depth; blk++) {
+        w += 2 * D;
+        pack((int)(3 * D), (int)D, w, o); o += 3 * D * D; w += 3 * D * D + 3 * D;
+        pack((int)D, (int)D, w, o); o += D * D; w += D * D + D;
+        w += 2 * D;
+        pack((int)Mh, (int)D, w, o); o += Mh * D; w += Mh * D + Mh;
+        pack((int)D, (int)Mh, w, o); o += D * Mh; w += D * Mh + D;
+    }
+    OS_HIP(ctx, hipGetLastError());
+    OS_HIP(ctx, hipStreamSynchronize(0));
+    return 0;
+}
+
+int os_vit_encode(os_ctx *ctx, int32_t N, const float *images, float *latent, void *stream)
+{
+    OS_CHECK_CTX(ctx);
+    os_vit_state *v = (os_vit_state *)ctx->vit;
+    if (!v || !v->w) return os_fail(ctx, -5, "os_vit_encode: call os_vit_load first");
+    if (N <= 0 || !images || !latent) return os_fail(ctx, -2, "os_vit_encode: bad argument");
+    OS_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = (hipStream_t)stream;
+    const VitDims &d = v->d;
+    const int D = d.dim, L = ntok(d), G = grid_of(d), PP = d.patch * d.patch, Mh = d.mlp;
+    const size_t M = (size_t)N * L, Mp = (size_t)N * G * G;
+    // scratch: X [M][D] (token matrix) | Y [M][D] | big [M][max(3D, mlp)]
+    const size_t bigw = (size_t)(3 * D > Mh ? 3 * D : Mh);
+    const size_t need = M * D * 2 + M * bigw;
+    if (os_ensure_scratch(ctx, &v->buf, &v->buf_floats, need)) return -10;
+    float *X = v->buf, *Y = X + M * D, *big = Y + M * D;
+    const float *w = v->w;
+    const float *wp = v->wp;
+    const float *patch_b = w + (size_t)D * PP, *cls = patch_b + D, *pos = cls + D;
+    w = pos + (size_t)L * D;
+    GemmArgs g;
+    g.img = images; g.img_size = d.img; g.grid = G; g.pos = pos; g.L = L; g.A = nullptr; g.lda = 0;
+    // patch embedding straight from the images into the token matrix (+ patch bias + position table); cls rows beside it
+    g.M = Mp; g.N = D; g.K = PP; g.Wp = wp; g.bias = patch_b; g.C = X;
+    g.patch = d.patch;
+    launch_gemm<1, 3>(ctx, g, s, "vit_gemm_kernel<patch,+pos>");
+    wp += (size_t)D * PP;
+    {
+        const int slot = os_prof_begin(ctx, OS_PHASE_VIT_MISC, s, "cls_row_kernel");
+        hipLaunchKernelGGL(cls_row_kernel, dim3((N * D + 255) / 256), dim3(256), 0, s, N, L, D, cls, pos, X);
+        os_prof_end(ctx, slot, s);
+    }
+    OS_HIP(ctx, hipGetLastError());
+    if (int rc = os_vit_run_blocks(ctx, v, d, w, wp, X, Y, big, N, s, &w)) return rc;
     const float *nw = w; w += D; const float *nb = w;
     const int slot = os_prof_begin(ctx, OS_PHASE_VIT_MISC, s, "cls_head_kernel");
     hipLaunchKernelGGL(cls_head_kernel, dim3((N + 3) / 4), dim3(256), 0, s, N, L, D, X, nw, nb, latent);

@@ -1,9 +1,11 @@
-"""Encoder half of the reference's `Transformer_Autoencoder` (transformer/transformer_model.py:10-135) on the HIP path.
+"""The reference's `Transformer_Autoencoder` (transformer/transformer_model.py:10-175) on the HIP path.
 
 Same constructor signature and the same `state_dict` keys for the encoder (timm 0.3.2 naming: patch_embed.proj.*,
 cls_token, pos_embed, blocks.{i}.norm1/attn.qkv/attn.proj/norm2/mlp.fc1/mlp.fc2.*, norm.*), so a checkpoint saved by
-`transformer/autoencoder_training.py:128-131` loads with `load_state_dict(..., strict=False)` (decoder keys are
-ignored: the decoder and its loss are training-only and out of scope).  `forward_encoder(x)` takes (N,1,224,224) in [0,1]
+`transformer/autoencoder_training.py:128-131` loads with `load_state_dict(..., strict=False)` into the default, encoder-only
+module and strictly into `Transformer_Autoencoder(decoder=True)`, which adds decoder_embed, decoder_noise_token,
+decoder_pos_embed, decoder_blocks.{i}.*, decoder_norm and decoder_pred and runs forward / forward_decoder / forward_loss /
+reconstruct through `os_vit_decode` (transformer/autoencoder_load.py:57-67).  `forward_encoder(x)` takes (N,1,224,224) in [0,1]
 (gru/gru_test.py:49-53) and returns (N,1,128) like the reference; it runs `os_vit_encode` (hand-written HIP kernels only: fp32-MFMA GEMM with fused epilogues, MFMA attention).
 Parity: the reference's own class (unmodified glue: patch + position table, cls token, block loop, final LayerNorm, token 0, sigmoid)
 around a plain-torch restatement of the timm-0.3.2 blocks (golden G11) and around Hugging Face transformers' ViTLayer (G14: identical
@@ -61,9 +63,20 @@ class _PatchEmbed(nn.Module):
         self.proj = nn.Conv2d(in_chans, embed_dim, kernel_size=patch_size, stride=patch_size)
 
 
+_BLOCK_KEYS = ("norm1.weight", "norm1.bias", "attn.qkv.weight", "attn.qkv.bias", "attn.proj.weight", "attn.proj.bias",
+               "norm2.weight", "norm2.bias", "mlp.fc1.weight", "mlp.fc1.bias", "mlp.fc2.weight", "mlp.fc2.bias")
+
+
 class Transformer_Autoencoder(nn.Module):
+    """The reference's constructor arguments, then `decoder`.  With decoder=False (default) the module is the encoder alone:
+    encoder keys only, and forward() raises NotImplementedError.  With decoder=True it also owns the reference's decoder_*
+    parameters under the reference's names (a reference checkpoint loads strictly) and forward / forward_decoder / forward_loss /
+    patchify / unpatchify return what the reference's return; reconstruct(imgs) is unpatchify(forward(imgs)[1]) in one call.
+    A context holds ONE auto-encoder: another module's call on the same engine evicts this one's weights."""
+
     def __init__(self, img_size=224, patch_size=16, in_chans=1, embed_dim=128, depth=3, num_heads=4,
-                 decoder_embed_dim=128, decoder_depth=3, decoder_num_heads=4, mlp_ratio=4., norm_layer=nn.LayerNorm):
+                 decoder_embed_dim=128, decoder_depth=3, decoder_num_heads=4, mlp_ratio=4., norm_layer=nn.LayerNorm,
+                 decoder=False):
         super().__init__()
         self.in_chans, self.img_size, self.patch_size = in_chans, img_size, patch_size
         self.embed_dim, self.depth, self.num_heads = embed_dim, depth, num_heads
@@ -74,7 +87,20 @@ class Transformer_Autoencoder(nn.Module):
         self.pos_embed = nn.Parameter(torch.zeros(1, self.num_patches + 1, embed_dim), requires_grad=False)
         self.blocks = nn.ModuleList([_Block(embed_dim, self.mlp_hidden) for _ in range(depth)])
         self.norm = nn.LayerNorm(embed_dim)
-        self.pos_embed.data.copy_(torch.from_numpy(_sincos_pos_embed(embed_dim, int(self.num_patches ** .5))).float().unsqueeze(0))
+        grid = int(self.num_patches ** .5)
+        self.pos_embed.data.copy_(torch.from_numpy(_sincos_pos_embed(embed_dim, grid)).float().unsqueeze(0))
+        self.has_decoder = bool(decoder)
+        if self.has_decoder:                                           # transformer_model.py:36-47
+            self.decoder_embed_dim, self.decoder_depth, self.decoder_num_heads = decoder_embed_dim, decoder_depth, decoder_num_heads
+            self.decoder_mlp_hidden = int(decoder_embed_dim * mlp_ratio)
+            self.decoder_embed = nn.Linear(embed_dim, decoder_embed_dim, bias=True)
+            self.decoder_noise_token = nn.Parameter(torch.zeros(1, 1, decoder_embed_dim))
+            self.decoder_pos_embed = nn.Parameter(torch.zeros(1, self.num_patches + 1, decoder_embed_dim), requires_grad=False)
+            self.decoder_blocks = nn.ModuleList([_Block(decoder_embed_dim, self.decoder_mlp_hidden) for _ in range(decoder_depth)])
+            self.decoder_norm = nn.LayerNorm(decoder_embed_dim)
+            self.decoder_pred = nn.Linear(decoder_embed_dim, patch_size ** 2 * in_chans, bias=True)
+            self.decoder_pos_embed.data.copy_(torch.from_numpy(_sincos_pos_embed(decoder_embed_dim, grid)).float().unsqueeze(0))
+            torch.nn.init.normal_(self.decoder_noise_token, std=.02)   # transformer_model.py:69
         torch.nn.init.normal_(self.cls_token, std=.02)                 # transformer_model.py:66
         w = self.patch_embed.proj.weight.data
         torch.nn.init.xavier_uniform_(w.view([w.shape[0], -1]))        # transformer_model.py:62-63
@@ -90,36 +116,128 @@ class Transformer_Autoencoder(nn.Module):
         parts = [sd["patch_embed.proj.weight"].reshape(-1), sd["patch_embed.proj.bias"], sd["cls_token"].reshape(-1),
                  sd["pos_embed"].reshape(-1)]
         for i in range(self.depth):
-            p = f"blocks.{i}."
-            for k in ("norm1.weight", "norm1.bias", "attn.qkv.weight", "attn.qkv.bias", "attn.proj.weight", "attn.proj.bias",
-                      "norm2.weight", "norm2.bias", "mlp.fc1.weight", "mlp.fc1.bias", "mlp.fc2.weight", "mlp.fc2.bias"):
-                parts.append(sd[p + k].reshape(-1))
+            parts += [sd[f"blocks.{i}.{k}"].reshape(-1) for k in _BLOCK_KEYS]
         parts += [sd["norm.weight"], sd["norm.bias"]]
         return torch.cat([t.detach().float().reshape(-1) for t in parts]).to(dev).contiguous()
+
+    def _flat_decoder(self, dev):
+        """include/optistate_hip.h (os_vit_load_decoder): the decoder's flat weight vector."""
+        sd = self.state_dict()
+        parts = [sd["decoder_embed.weight"], sd["decoder_embed.bias"], sd["decoder_noise_token"], sd["decoder_pos_embed"]]
+        for i in range(self.decoder_depth):
+            parts += [sd[f"decoder_blocks.{i}.{k}"] for k in _BLOCK_KEYS]
+        parts += [sd["decoder_norm.weight"], sd["decoder_norm.bias"], sd["decoder_pred.weight"], sd["decoder_pred.bias"]]
+        return torch.cat([t.detach().float().reshape(-1) for t in parts]).to(dev).contiguous()
+
+    def _decoder_dims(self):
+        return _capi.OsVitDims(self.img_size, self.patch_size, self.in_chans, self.decoder_embed_dim, self.decoder_depth,
+                               self.decoder_num_heads, self.decoder_mlp_hidden)
+
+    def _engine(self, t):
+        if not t.is_cuda:
+            raise RuntimeError("optistate_amd Transformer_Autoencoder needs a tensor on the MI355X (no CPU fallback)")
+        return default_engine(t.device.index or 0)         # the calling thread's context on this GPU
 
     def forward_encoder(self, x):
         if not x.is_cuda:
             raise RuntimeError("optistate_amd Transformer_Autoencoder.forward_encoder needs a tensor on the MI355X (no CPU fallback)")
         eng = default_engine(x.device.index or 0)          # the calling thread's context on this GPU
-        with eng.lock:                                     # load + encode as one unit: a context holds ONE encoder
+        with eng.lock:                                     # load + encode as one unit: a context holds ONE auto-encoder
             return self._encode_locked(eng, x)
 
-    def _encode_locked(self, eng, x):
+    def _load_locked(self, eng, dev):
         versions = tuple((p.data_ptr(), p._version) for p in self.parameters())
-        if self._loaded is None or self._loaded[0] != versions or getattr(eng, "_vit_owner", None) is not self:
-            flat = self._flat(x.device)
-            d = _capi.OsVitDims(self.img_size, self.patch_size, self.in_chans, self.embed_dim, self.depth, self.num_heads,
-                                self.mlp_hidden)
-            assert flat.numel() == eng.lib.os_vit_param_count(C.byref(d)), "flat ViT weight vector has the wrong length"
-            eng._check(eng.lib.os_vit_load(eng._h, C.byref(d), _ptr(flat)), "os_vit_load")
-            self._loaded = (versions, flat)        # keep the flat tensor alive: the library references it
-            eng._vit_owner = self                  # a context holds ONE encoder: another module's load evicts this one
+        if self._loaded is not None and self._loaded[0] == versions and getattr(eng, "_vit_owner", None) is self:
+            return
+        flat = self._flat(dev)
+        d = _capi.OsVitDims(self.img_size, self.patch_size, self.in_chans, self.embed_dim, self.depth, self.num_heads,
+                            self.mlp_hidden)
+        assert flat.numel() == eng.lib.os_vit_param_count(C.byref(d)), "flat ViT weight vector has the wrong length"
+        eng._check(eng.lib.os_vit_load(eng._h, C.byref(d), _ptr(flat)), "os_vit_load")
+        dflat = None
+        if self.has_decoder:
+            dflat, dd = self._flat_decoder(dev), self._decoder_dims()
+            assert dflat.numel() == eng.lib.os_vit_decoder_param_count(C.byref(dd), self.embed_dim), \
+                "flat ViT decoder weight vector has the wrong length"
+            eng._check(eng.lib.os_vit_load_decoder(eng._h, C.byref(dd), self.embed_dim, _ptr(dflat)), "os_vit_load_decoder")
+        self._loaded = (versions, flat, dflat)     # keep the flat tensors alive: the library references them
+        eng._vit_owner = self                      # a context holds ONE auto-encoder: another module's load evicts this one
+
+    def _encode_locked(self, eng, x):
+        self._load_locked(eng, x.device)
         N = x.shape[0]
         img = x.reshape(N, self.img_size, self.img_size).to(torch.float32).contiguous()
         lat = torch.empty((N, self.embed_dim), dtype=torch.float32, device=x.device)
         eng._check(eng.lib.os_vit_encode(eng._h, N, _ptr(img), _ptr(lat), eng._stream()), "os_vit_encode")
         return lat.reshape(N, 1, self.embed_dim)
 
-    def forward(self, *a, **k):
-        raise NotImplementedError("only forward_encoder (the latent used by the GRU, gru/gru_test.py:119-132) is implemented; "
-                                  "the decoder and reconstruction loss are training-only and out of scope")
+    def _need_decoder(self):
+        if not self.has_decoder:
+            raise NotImplementedError("only forward_encoder (the latent used by the GRU, gru/gru_test.py:119-132) is implemented; "
+                                      "the decoder and reconstruction loss need Transformer_Autoencoder(..., decoder=True)")
+
+    def _decode_locked(self, eng, latent, img, want_pred, want_recon, want_loss):
+        """One os_vit_decode: latent (N,1,D) -> (pred | None, recon | None, loss | None)."""
+        self._load_locked(eng, latent.device)
+        N, dev = latent.shape[0], latent.device
+        lat = latent.reshape(N, self.embed_dim).to(torch.float32).contiguous()
+        pred = torch.empty((N, self.num_patches, self.patch_size ** 2 * self.in_chans), dtype=torch.float32, device=dev) if want_pred else None
+        recon = torch.empty((N, self.in_chans, self.img_size, self.img_size), dtype=torch.float32, device=dev) if want_recon else None
+        loss = torch.empty((), dtype=torch.float32, device=dev) if want_loss else None
+        eng._check(eng.lib.os_vit_decode(eng._h, N, _ptr(lat), _ptr(img) if want_loss else None, _ptr(pred), _ptr(recon), _ptr(loss),
+                                         eng._stream()), "os_vit_decode")
+        return pred, recon, loss
+
+    def _frames(self, imgs):
+        return imgs.reshape(imgs.shape[0], self.img_size, self.img_size).to(torch.float32).contiguous()
+
+    def forward_decoder(self, x):
+        """latent (N,1,embed_dim) -> pred (N, num_patches, patch_size**2 * in_chans)   (transformer_model.py:137-159)"""
+        self._need_decoder()
+        eng = self._engine(x)
+        with eng.lock:
+            return self._decode_locked(eng, x, None, True, False, False)[0]
+
+    def forward_loss(self, imgs, pred):
+        """mean((patchify(imgs) - pred)**2) as a 0-d device tensor   (transformer_model.py:161-169)"""
+        self._need_decoder()
+        eng = self._engine(pred)
+        with eng.lock:
+            self._load_locked(eng, pred.device)
+            loss = torch.empty((), dtype=torch.float32, device=pred.device)
+            eng._check(eng.lib.os_vit_recon_loss(eng._h, pred.shape[0], _ptr(self._frames(imgs)), _ptr(pred.to(torch.float32).contiguous()),
+                                                 _ptr(loss), eng._stream()), "os_vit_recon_loss")
+        return loss
+
+    def forward(self, imgs):
+        """(loss, pred) like the reference (transformer_model.py:171-175): os_vit_encode + one os_vit_decode."""
+        self._need_decoder()
+        eng = self._engine(imgs)
+        with eng.lock:
+            lat = self._encode_locked(eng, imgs)
+            pred, _, loss = self._decode_locked(eng, lat, self._frames(imgs), True, False, True)
+        return loss, pred
+
+    def reconstruct(self, imgs):
+        """imgs (N,1,H,W) -> the decoder's image (N,1,H,W) = unpatchify(forward(imgs)[1]), written by the decoder's last kernel."""
+        self._need_decoder()
+        eng = self._engine(imgs)
+        with eng.lock:
+            lat = self._encode_locked(eng, imgs)
+            return self._decode_locked(eng, lat, None, False, True, False)[1]
+
+    def patchify(self, imgs):
+        """(N, in_chans, H, W) -> (N, L, patch_size**2 * in_chans)   (transformer_model.py:84-96)"""
+        p = self.patch_size
+        assert imgs.shape[2] == imgs.shape[3] and imgs.shape[2] % p == 0
+        h = w = imgs.shape[2] // p
+        x = imgs.reshape(imgs.shape[0], self.in_chans, h, p, w, p)
+        return torch.einsum("nchpwq->nhwpqc", x).reshape(imgs.shape[0], h * w, p ** 2 * self.in_chans)
+
+    def unpatchify(self, x):
+        """(N, L, patch_size**2 * in_chans) -> (N, in_chans, H, W)   (transformer_model.py:98-110)"""
+        p = self.patch_size
+        h = w = int(x.shape[1] ** .5)
+        assert h * w == x.shape[1]
+        x = x.reshape(x.shape[0], h, w, p, p, self.in_chans)
+        return torch.einsum("nhwpqc->nchpwq", x).reshape(x.shape[0], self.in_chans, h * p, h * p)
