@@ -356,6 +356,24 @@ int os_vit_decode(os_ctx *ctx, int32_t N, const float *latent, const float *imag
                   void *stream);
 int os_vit_recon_loss(os_ctx *ctx, int32_t N, const float *images, const float *pred, float *loss, void *stream);
 
+/* Training step of the auto-encoder (transformer/autoencoder_training.py:103-114) for the pair loaded by os_vit_load and
+ * os_vit_load_decoder (same image geometry, latent_dim = the encoder's embed_dim).  Supported: everything the two loads accept
+ * with a head dimension of 32 and at most 224 tokens in encoder and decoder (their widths may differ); anything else returns -4
+ * with a message (os_vit_train_ws_floats: 0).
+ * os_vit_train_ws_floats: floats of the caller-owned workspace for N images.
+ * os_vit_forward_train: encoder + decoder + loss as os_vit_encode / os_vit_decode compute them (unfused launches), keeping in ws
+ * what the backward needs: per block its input, qkv, attention output, the residual stream behind the attention, the fc1
+ * pre-activation and its GELU; the encoder's latent; pred.  pred [N][L-1][PP] may be null; loss is one device float.
+ * os_vit_backward: from ws, the same images and dloss (one DEVICE float, d objective / d loss) the gradients of every weight in
+ * the flat layouts of os_vit_param_count (grad_enc) and os_vit_decoder_param_count (grad_dec).  Both vectors are overwritten,
+ * not accumulated into; the slots of pos_embed / decoder_pos_embed are written as zero.  The weights must be the ones the
+ * forward ran with (still loaded).  All reductions are ordered (per-slice partials added in ascending order, no atomics): the
+ * same inputs give the same bits.  Both calls are stream-ordered and allocate only on the first call at a given N. */
+size_t os_vit_train_ws_floats(os_ctx *ctx, int32_t N);
+int os_vit_forward_train(os_ctx *ctx, int32_t N, const float *images, float *ws, float *pred, float *loss, void *stream);
+int os_vit_backward(os_ctx *ctx, int32_t N, const float *images, const float *ws, const float *dloss, float *grad_enc,
+                    float *grad_dec, void *stream);
+
 /* ---- Convex-MPC ground-reaction forces ("next" row f.2): the QP the reference solves with casadi + qpOASES inside
  * predict_mpc (misc/force_controller.py:70-162 builds it, kalman_filter/kalman_filter.py:141-152 fills the parameters
  * and takes column 0 of the solution).  N = 5 horizon steps x 12 forces; per trajectory:

@@ -242,14 +242,6 @@ __global__ __launch_bounds__(256) void dec_loss_finish_kernel(int n, const doubl
 
 using namespace osv;
 
-struct os_vit_dec_state {
-    VitDims d;               // dim / depth / heads / mlp are the decoder's
-    int latent_dim;
-    const float *w;          // caller-owned flat weights
-    float *wp; size_t wp_floats;       // per block qkv, proj, fc1, fc2, then decoder_pred, in B-fragment order
-    float *part; size_t part_floats;   // float64 loss partials
-};
-
 static size_t dec_block_floats(const VitDims &d)
 {
     const size_t D = d.dim, Mh = d.mlp;
@@ -286,6 +278,40 @@ static int dec_finish_loss(os_ctx *ctx, int nparts, const double *partials, doub
     hipLaunchKernelGGL(dec_loss_finish_kernel, dim3(1), dim3(256), 0, s, nparts, partials, 1.0 / count, loss);
     os_prof_end(ctx, slot, s);
     OS_HIP(ctx, hipGetLastError());
+    return 0;
+}
+
+int os_vit_dec_seed(os_ctx *ctx, const os_vit_dec_state *q, int N, const float *latent, float *X, hipStream_t s)
+{
+    const int D = q->d.dim, L = ntok(q->d), De = q->latent_dim;
+    const float *We = q->w, *be = We + (size_t)D * De, *noise = be + D, *dpos = noise + D;
+    const int slot = os_prof_begin(ctx, OS_PHASE_VIT_MISC, s, "dec_seed_kernel");
+    hipLaunchKernelGGL(dec_seed_kernel, dim3(N), dim3(256), 0, s, L, D, De, We, be, noise, dpos, latent, X);
+    os_prof_end(ctx, slot, s);
+    OS_HIP(ctx, hipGetLastError());
+    return 0;
+}
+
+// decoder_norm (flat cursor w) + decoder_pred over the patch rows of X, with the loss when asked for
+int os_vit_dec_tail(os_ctx *ctx, os_vit_dec_state *q, int N, const float *w, const float *X, const float *images, float *pred,
+                    float *recon, float *loss, hipStream_t s)
+{
+    const VitDims &d = q->d;
+    const int D = d.dim, L = ntok(d), NP = d.patch * d.patch, Mh = d.mlp;
+    const uint32_t Mp = (uint32_t)N * (L - 1);
+    const int ntiles = (int)((Mp + DP_BM - 1) / DP_BM);
+    if (loss && os_ensure_scratch(ctx, &q->part, &q->part_floats, (size_t)2 * ntiles)) return -10;
+    PredArgs a;
+    a.M = Mp; a.L = L; a.G = grid_of(d); a.P = d.patch; a.NP = NP; a.X = X;
+    a.lnw = w; a.lnb = w + D; a.bias = w + 2 * D + (size_t)NP * D;
+    a.Wp = q->wp + (size_t)d.depth * (3 * D * D + D * D + 2 * (size_t)Mh * D);
+    a.images = loss ? images : nullptr; a.pred = pred; a.recon = recon; a.partials = loss ? (double *)q->part : nullptr;
+    const int slot = os_prof_begin(ctx, OS_PHASE_VIT_GEMM, s, "dec_pred_kernel");
+    if (D == 128) hipLaunchKernelGGL(dec_pred_kernel<128>, dim3(ntiles), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(dec_pred_kernel<256>, dim3(ntiles), dim3(256), 0, s, a);
+    os_prof_end(ctx, slot, s);
+    OS_HIP(ctx, hipGetLastError());
+    if (loss) return dec_finish_loss(ctx, ntiles, a.partials, (double)Mp * NP, loss, s);
     return 0;
 }
 
@@ -344,7 +370,7 @@ int os_vit_decode(os_ctx *ctx, int32_t N, const float *latent, const float *imag
     if (N <= 0 || !latent) return os_fail(ctx, -2, "os_vit_decode: bad argument");
     if (loss && !images) return os_fail(ctx, -2, "os_vit_decode: the loss needs the images");
     const VitDims &d = q->d;
-    const int D = d.dim, L = ntok(d), G = grid_of(d), NP = d.patch * d.patch, Mh = d.mlp, De = q->latent_dim;
+    const int D = d.dim, L = ntok(d), Mh = d.mlp, De = q->latent_dim;
     if ((uint64_t)N * L >= (1ull << 31)) return os_fail(ctx, -2, "os_vit_decode: too many token rows for one call");
     OS_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t s = (hipStream_t)stream;
@@ -352,30 +378,11 @@ int os_vit_decode(os_ctx *ctx, int32_t N, const float *latent, const float *imag
     const size_t bigw = (size_t)(3 * D > Mh ? 3 * D : Mh);
     if (os_ensure_scratch(ctx, &v->buf, &v->buf_floats, M * D * 2 + M * bigw)) return -10;
     float *X = v->buf, *Y = X + M * D, *big = Y + M * D;
-    const uint32_t Mp = (uint32_t)N * (L - 1);
-    const int ntiles = (int)((Mp + DP_BM - 1) / DP_BM);
-    if (loss && os_ensure_scratch(ctx, &q->part, &q->part_floats, (size_t)2 * ntiles)) return -10;
-    const float *w = q->w;
-    const float *We = w, *be = We + (size_t)D * De, *noise = be + D, *dpos = noise + D;
-    w = dpos + (size_t)L * D;
-    int slot = os_prof_begin(ctx, OS_PHASE_VIT_MISC, s, "dec_seed_kernel");
-    hipLaunchKernelGGL(dec_seed_kernel, dim3(N), dim3(256), 0, s, L, D, De, We, be, noise, dpos, latent, X);
-    os_prof_end(ctx, slot, s);
-    OS_HIP(ctx, hipGetLastError());
+    if (int rc = os_vit_dec_seed(ctx, q, N, latent, X, s)) return rc;
+    const float *w = q->w + (size_t)D * De + 2 * D + (size_t)L * D;
     if (int rc = os_vit_run_blocks(ctx, v, d, w, q->wp, X, Y, big, N, s, &w)) return rc;
     if (!pred && !recon && !loss) return 0;
-    PredArgs a;
-    a.M = Mp; a.L = L; a.G = G; a.P = d.patch; a.NP = NP; a.X = X;
-    a.lnw = w; a.lnb = w + D; a.bias = w + 2 * D + (size_t)NP * D;
-    a.Wp = q->wp + (size_t)d.depth * (3 * D * D + D * D + 2 * (size_t)Mh * D);
-    a.images = loss ? images : nullptr; a.pred = pred; a.recon = recon; a.partials = loss ? (double *)q->part : nullptr;
-    slot = os_prof_begin(ctx, OS_PHASE_VIT_GEMM, s, "dec_pred_kernel");
-    if (D == 128) hipLaunchKernelGGL(dec_pred_kernel<128>, dim3(ntiles), dim3(256), 0, s, a);
-    else hipLaunchKernelGGL(dec_pred_kernel<256>, dim3(ntiles), dim3(256), 0, s, a);
-    os_prof_end(ctx, slot, s);
-    OS_HIP(ctx, hipGetLastError());
-    if (loss) return dec_finish_loss(ctx, ntiles, a.partials, (double)Mp * NP, loss, s);
-    return 0;
+    return os_vit_dec_tail(ctx, q, N, w, X, images, pred, recon, loss, s);
 }
 
 int os_vit_recon_loss(os_ctx *ctx, int32_t N, const float *images, const float *pred, float *loss, void *stream)

@@ -434,19 +434,9 @@ __global__ __launch_bounds__(NW * 64, 1) void attention_mfma_dma_kernel(int L, i
 // SRC: 0 row-major A [M][lda]; 1 patches taken straight from the images (row = (frame, gy, gx), column = 16 py + px).
 // EPI: 0 C = acc + bias; 1 C = gelu(acc + bias) (exact erf form); 2 X += acc + bias (residual, in place);
 //      3 X[frame*L + 1 + p] = acc + bias + pos[1 + p] (patch embedding into the token matrix).
-struct GemmArgs {
-    size_t M;
-    int N, K, lda;
-    const float *A;            // SRC 0
-    const float *img;          // SRC 1: [frames][img][img]
-    int img_size, grid, patch; // SRC 1
-    const float *Wp;           // packed weights
-    const float *bias;         // [N]
-    float *C;                  // EPI 0/1: [M][N]; EPI 2/3: the token matrix X
-    const float *pos;          // EPI 3: [L][N]
-    int L;                     // EPI 3
-};
-
+//      The training step's (vit_train.hip): 4 C = acc + bias + R (residual out of place: the block's input survives);
+//      5 C = acc + bias and C2 = gelu(C) (fc1 with its pre-activation kept); 7 C = acc (input gradients, no bias).
+// (GemmArgs: vit_host.hpp)
 constexpr int GM_BM = 128, GM_KC = 128;
 
 
@@ -589,7 +579,7 @@ __global__ __launch_bounds__(256, 2) void vit_gemm_kernel(const GemmArgs a)
     // Epilogue through a buffer descriptor over the output: offset = per-lane constant + SGPR row offset, rows past M fall
     // outside the descriptor's range and are dropped by the hardware (no per-element address arithmetic or bounds test).
     const int col = chunk * 32 + li;
-    const float bv = a.bias[col];
+    const float bv = EPI == 7 ? 0.f : a.bias[col];
     if (EPI == 3) {
         // (frame, patch) of the lane's first row by division once; its other 63 rows lie at most 127 further on, so with at
         // least 128 patches per frame there is at most one carry (a division per element was ~30 instructions x 64)
@@ -610,6 +600,7 @@ __global__ __launch_bounds__(256, 2) void vit_gemm_kernel(const GemmArgs a)
         return;
     }
     const osk::rsrc_t rc = osk::make_rsrc(a.C, (uint32_t)(a.M * (size_t)a.N * 4));
+    const osk::rsrc_t rx = osk::make_rsrc(EPI == 5 ? a.C2 : (EPI == 4 ? a.R : a.C), (uint32_t)(a.M * (size_t)a.N * 4));   // EPI 4 / 5
     const uint32_t vo = (uint32_t)((4 * lh) * a.N + col) * 4u, rowb = (uint32_t)a.N * 4u;
 #pragma unroll
     for (int rb = 0; rb < 4; rb++)
@@ -619,6 +610,8 @@ __global__ __launch_bounds__(256, 2) void vit_gemm_kernel(const GemmArgs a)
             float v = acc[rb][e] + bv;
             if (EPI == 1) v = gelu_erf(v);
             if (EPI == 2) v += osk::buf_load(rc, vo, so);
+            if (EPI == 4) v += osk::buf_load(rx, vo, so);
+            if (EPI == 5) osk::buf_store(rx, vo, so, gelu_erf(v));
             osk::buf_store(rc, vo, so, v);
         }
 }
@@ -1034,6 +1027,7 @@ void os_vit_destroy(os_ctx *ctx)
     if (!v) return;
     os_vit_decoder_destroy(v);
     if (v->buf) (void)hipFree(v->buf);
+    if (v->tbuf) (void)hipFree(v->tbuf);
     if (v->wp) (void)hipFree(v->wp);
     free(v);
     ctx->vit = nullptr;
@@ -1064,11 +1058,68 @@ void os_vit_pack_w(int N, int K, const float *W, float *dst, hipStream_t s)
     hipLaunchKernelGGL(vit_pack_w_kernel, dim3(256), dim3(256), 0, s, N, K, W, dst);
 }
 
+int os_vit_launch_attention(os_ctx *ctx, os_vit_state *v, const VitDims &d, int N, const float *big, const float *qkvb, float *Y, hipStream_t s)
+{
+    const int D = d.dim, L = ntok(d), hd = D / d.heads;
+    const size_t alds = (size_t)2 * L * (hd + 1) * sizeof(float);
+    const int ntl = (L + 31) / 32;
+    const int slot = os_prof_begin(ctx, OS_PHASE_VIT_ATTN, s, (hd == 32 && ntl == 7) ? (ctx->tune_vit_att_dma ? "attention_mfma_dma_kernel<7>" : "attention_mfma_kernel<7>") : "attention_kernel");
+    if (hd == 32 && ntl == 7) {              // the reference's shape: 197 tokens, head_dim 32 -> matrix cores
+        const size_t mlds = (size_t)2 * L * 33 * sizeof(float);
+        if (!v->att_attr_set) {
+            OS_HIP(ctx, hipFuncSetAttribute((const void *)attention_mfma_kernel<7>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+            OS_HIP(ctx, hipFuncSetAttribute((const void *)attention_mfma_dma_kernel<7>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+            v->att_attr_set = true;
+        }
+        const int nitems = N * d.heads, cus = ctx->cu_count > 0 ? ctx->cu_count : 256;
+        if (ctx->tune_vit_att_dma) {          // persistent workgroups, K / V of the next head by LDS-DMA underneath the current one
+            const size_t dlds = (size_t)2 * L * (36 + 32) * sizeof(float);
+            hipLaunchKernelGGL(attention_mfma_dma_kernel<7>, dim3(nitems < cus ? nitems : cus), dim3(512), dlds, s, L, D, d.heads, nitems, big, Y);
+        } else
+            hipLaunchKernelGGL(attention_mfma_kernel<7>, dim3(N * d.heads), dim3(512), mlds, s, L, D, d.heads, big, qkvb, Y);
+    } else if (hd == 32) hipLaunchKernelGGL(attention_kernel<32>, dim3(N * d.heads), dim3(256), alds, s, L, D, d.heads, big, qkvb, Y);
+    else hipLaunchKernelGGL(attention_kernel<64>, dim3(N * d.heads), dim3(256), alds, s, L, D, d.heads, big, qkvb, Y);
+    os_prof_end(ctx, slot, s);
+    return 0;
+}
+
+void os_vit_launch_layernorm(os_ctx *ctx, size_t M, int D, const float *X, const float *w, const float *b, float *Y, hipStream_t s)
+{
+    const int slot = os_prof_begin(ctx, OS_PHASE_VIT_MISC, s, "layernorm_kernel");
+    hipLaunchKernelGGL(layernorm_kernel, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, s, M, D, X, w, b, Y, (size_t)D);
+    os_prof_end(ctx, slot, s);
+}
+
+int os_vit_launch_gemm(os_ctx *ctx, int src, int epi, const GemmArgs &g, hipStream_t s, const char *name)
+{
+    if (src == 1 && epi == 3) launch_gemm<1, 3>(ctx, g, s, name);
+    else if (src == 0 && epi == 0) launch_gemm<0, 0>(ctx, g, s, name);
+    else if (src == 0 && epi == 4) launch_gemm<0, 4>(ctx, g, s, name);
+    else if (src == 0 && epi == 5) launch_gemm<0, 5>(ctx, g, s, name);
+    else if (src == 0 && epi == 7) launch_gemm<0, 7>(ctx, g, s, name);
+    else return os_fail(ctx, -2, "os_vit_launch_gemm: no such variant");
+    return 0;
+}
+
+void os_vit_launch_cls_row(os_ctx *ctx, int N, int L, int D, const float *cls, const float *pos, float *X, hipStream_t s)
+{
+    const int slot = os_prof_begin(ctx, OS_PHASE_VIT_MISC, s, "cls_row_kernel");
+    hipLaunchKernelGGL(cls_row_kernel, dim3((N * D + 255) / 256), dim3(256), 0, s, N, L, D, cls, pos, X);
+    os_prof_end(ctx, slot, s);
+}
+
+void os_vit_launch_cls_head(os_ctx *ctx, int N, int L, int D, const float *X, const float *w, const float *b, float *latent, hipStream_t s)
+{
+    const int slot = os_prof_begin(ctx, OS_PHASE_VIT_MISC, s, "cls_head_kernel");
+    hipLaunchKernelGGL(cls_head_kernel, dim3((N + 3) / 4), dim3(256), 0, s, N, L, D, X, w, b, latent);
+    os_prof_end(ctx, slot, s);
+}
+
 // the block loop of encoder and decoder (contract in vit_host.hpp)
 int os_vit_run_blocks(os_ctx *ctx, os_vit_state *v, const VitDims &d, const float *w, const float *wp, float *X, float *Y,
                       float *big, int N, hipStream_t s, const float **w_end)
 {
-    const int D = d.dim, L = ntok(d), Mh = d.mlp, hd = D / d.heads;
+    const int D = d.dim, L = ntok(d), Mh = d.mlp;
     const size_t M = (size_t)N * L;
     GemmArgs g;
     g.img = nullptr; g.img_size = 0; g.grid = 0; g.patch = 0; g.pos = nullptr; g.L = L; g.M = M;
@@ -1091,25 +1142,7 @@ int os_vit_run_blocks(os_ctx *ctx, os_vit_state *v, const VitDims &d, const floa
             launch_gemm<0, 0>(ctx, g, s, "vit_gemm_kernel<+bias>");
         }
         wp += (size_t)3 * D * D;
-        const size_t alds = (size_t)2 * L * (hd + 1) * sizeof(float);
-        const int ntl = (L + 31) / 32;
-        slot = os_prof_begin(ctx, OS_PHASE_VIT_ATTN, s, (hd == 32 && ntl == 7) ? (ctx->tune_vit_att_dma ? "attention_mfma_dma_kernel<7>" : "attention_mfma_kernel<7>") : "attention_kernel");
-        if (hd == 32 && ntl == 7) {              // the reference's shape: 197 tokens, head_dim 32 -> matrix cores
-            const size_t mlds = (size_t)2 * L * 33 * sizeof(float);
-            if (!v->att_attr_set) {
-                OS_HIP(ctx, hipFuncSetAttribute((const void *)attention_mfma_kernel<7>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-                OS_HIP(ctx, hipFuncSetAttribute((const void *)attention_mfma_dma_kernel<7>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-                v->att_attr_set = true;
-            }
-            const int nitems = N * d.heads, cus = ctx->cu_count > 0 ? ctx->cu_count : 256;
-            if (ctx->tune_vit_att_dma) {          // persistent workgroups, K / V of the next head by LDS-DMA underneath the current one
-                const size_t dlds = (size_t)2 * L * (36 + 32) * sizeof(float);
-                hipLaunchKernelGGL(attention_mfma_dma_kernel<7>, dim3(nitems < cus ? nitems : cus), dim3(512), dlds, s, L, D, d.heads, nitems, big, Y);
-            } else
-                hipLaunchKernelGGL(attention_mfma_kernel<7>, dim3(N * d.heads), dim3(512), mlds, s, L, D, d.heads, big, qkvb, Y);
-        } else if (hd == 32) hipLaunchKernelGGL(attention_kernel<32>, dim3(N * d.heads), dim3(256), alds, s, L, D, d.heads, big, qkvb, Y);
-        else hipLaunchKernelGGL(attention_kernel<64>, dim3(N * d.heads), dim3(256), alds, s, L, D, d.heads, big, qkvb, Y);
-        os_prof_end(ctx, slot, s);
+        if (int rc = os_vit_launch_attention(ctx, v, d, N, big, qkvb, Y, s)) return rc;
         const bool mlp_fused = D == 128 && ctx->tune_vit_mlp_fused;
         const float *wproj = wp;
         if (!(mlp_fused && ctx->tune_vit_mlp_fused >= 2)) {
@@ -1249,17 +1282,11 @@ int os_vit_encode(os_ctx *ctx, int32_t N, const float *images, float *latent, vo
     g.patch = d.patch;
     launch_gemm<1, 3>(ctx, g, s, "vit_gemm_kernel<patch,+pos>");
     wp += (size_t)D * PP;
-    {
-        const int slot = os_prof_begin(ctx, OS_PHASE_VIT_MISC, s, "cls_row_kernel");
-        hipLaunchKernelGGL(cls_row_kernel, dim3((N * D + 255) / 256), dim3(256), 0, s, N, L, D, cls, pos, X);
-        os_prof_end(ctx, slot, s);
-    }
+    os_vit_launch_cls_row(ctx, N, L, D, cls, pos, X, s);
     OS_HIP(ctx, hipGetLastError());
     if (int rc = os_vit_run_blocks(ctx, v, d, w, wp, X, Y, big, N, s, &w)) return rc;
     const float *nw = w; w += D; const float *nb = w;
-    const int slot = os_prof_begin(ctx, OS_PHASE_VIT_MISC, s, "cls_head_kernel");
-    hipLaunchKernelGGL(cls_head_kernel, dim3((N + 3) / 4), dim3(256), 0, s, N, L, D, X, nw, nb, latent);
-    os_prof_end(ctx, slot, s);
+    os_vit_launch_cls_head(ctx, N, L, D, X, nw, nb, latent, s);
     OS_HIP(ctx, hipGetLastError());
     return 0;
 }

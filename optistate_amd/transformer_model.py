@@ -67,17 +67,65 @@ _BLOCK_KEYS = ("norm1.weight", "norm1.bias", "attn.qkv.weight", "attn.qkv.bias",
                "norm2.weight", "norm2.bias", "mlp.fc1.weight", "mlp.fc1.bias", "mlp.fc2.weight", "mlp.fc2.bias")
 
 
+class _VitTrainFn(torch.autograd.Function):
+    # Every forward owns its saved activations (a workspace tensor kept in the autograd ctx) and pins the flat weights it ran
+    # with, so any number of graphs may be alive at once (m(a)[0] + m(b)[0], gradient accumulation, another module's call in
+    # between: the engine's scratch and its loaded weights are shared per device).  pred is marked non-differentiable.
+    @staticmethod
+    def forward(ctx, imgs, module, *params):
+        eng = module._engine(imgs)
+        img = module._frames(imgs.detach())
+        N, dev = img.shape[0], img.device
+        with eng.lock:                                     # load + forward as one unit: a context holds ONE auto-encoder
+            module._load_locked(eng, dev)
+            _, flat, dflat = module._loaded
+            nws = eng.lib.os_vit_train_ws_floats(eng._h, N)
+            if nws == 0:
+                raise RuntimeError(f"os_vit_train_ws_floats: {eng.lib.os_last_error(eng._h).decode()}")
+            ws = torch.empty(nws, dtype=torch.float32, device=dev)
+            pred = torch.empty((N, module.num_patches, module.patch_size ** 2 * module.in_chans), dtype=torch.float32, device=dev)
+            loss = torch.empty((), dtype=torch.float32, device=dev)
+            eng._check(eng.lib.os_vit_forward_train(eng._h, N, _ptr(img), _ptr(ws), _ptr(pred), _ptr(loss), eng._stream()),
+                       "os_vit_forward_train")
+        ctx.module, ctx.eng = module, eng                 # backward runs on autograd's thread: the SAME context, not that thread's
+        ctx.save_for_backward(img, ws, flat, dflat)
+        ctx.mark_non_differentiable(pred)
+        return loss, pred
+
+    @staticmethod
+    def backward(ctx, dloss, _dpred):
+        img, ws, flat, dflat = ctx.saved_tensors
+        module, eng = ctx.module, ctx.eng
+        genc, gdec = torch.empty_like(flat), torch.empty_like(dflat)
+        with eng.lock:
+            module._load_flats_locked(eng, flat, dflat)    # the weights this forward ran with (usually still the loaded ones)
+            eng._check(eng.lib.os_vit_backward(eng._h, img.shape[0], _ptr(img), _ptr(ws), _ptr(dloss.to(torch.float32).contiguous()),
+                                               _ptr(genc), _ptr(gdec), eng._stream()), "os_vit_backward")
+        grads = []
+        for p, (which, off) in zip(module._train_params(), module._train_offsets()):
+            grads.append((genc if which == 0 else gdec)[off:off + p.numel()].view_as(p) if p.requires_grad else None)
+        return (None, None, *grads)
+
+
 class Transformer_Autoencoder(nn.Module):
     """The reference's constructor arguments, then `decoder`.  With decoder=False (default) the module is the encoder alone:
     encoder keys only, and forward() raises NotImplementedError.  With decoder=True it also owns the reference's decoder_*
     parameters under the reference's names (a reference checkpoint loads strictly) and forward / forward_decoder / forward_loss /
     patchify / unpatchify return what the reference's return; reconstruct(imgs) is unpatchify(forward(imgs)[1]) in one call.
-    A context holds ONE auto-encoder: another module's call on the same engine evicts this one's weights."""
+    A context holds ONE auto-encoder: another module's call on the same engine evicts this one's weights.
+    With decoder=True and trainable=True, forward(imgs) under enabled gradients returns a loss with a grad_fn: the reference's
+    training loop (transformer/autoencoder_training.py:103-114: loss.backward(), torch.optim.AdamW.step()) runs on the HIP forward
+    and backward (os_vit_forward_train / os_vit_backward); torch supplies memory, the autograd bookkeeping and the optimiser.
+    pos_embed and decoder_pos_embed stay fixed as in the reference, and pred is NOT differentiable (marked so): only the loss
+    carries the graph.  Under torch.no_grad() a trainable module takes the inference path."""
 
     def __init__(self, img_size=224, patch_size=16, in_chans=1, embed_dim=128, depth=3, num_heads=4,
                  decoder_embed_dim=128, decoder_depth=3, decoder_num_heads=4, mlp_ratio=4., norm_layer=nn.LayerNorm,
-                 decoder=False):
+                 decoder=False, trainable=False):
         super().__init__()
+        if trainable and not decoder:
+            raise ValueError("Transformer_Autoencoder(trainable=True) needs decoder=True: the loss is the decoder's")
+        self.trainable = bool(trainable)
         self.in_chans, self.img_size, self.patch_size = in_chans, img_size, patch_size
         self.embed_dim, self.depth, self.num_heads = embed_dim, depth, num_heads
         self.mlp_hidden = int(embed_dim * mlp_ratio)
@@ -129,6 +177,28 @@ class Transformer_Autoencoder(nn.Module):
         parts += [sd["decoder_norm.weight"], sd["decoder_norm.bias"], sd["decoder_pred.weight"], sd["decoder_pred.bias"]]
         return torch.cat([t.detach().float().reshape(-1) for t in parts]).to(dev).contiguous()
 
+    def _train_params(self):
+        """Parameters in the order of the two flat layouts (_flat, then _flat_decoder)."""
+        ps = [self.patch_embed.proj.weight, self.patch_embed.proj.bias, self.cls_token, self.pos_embed]
+        for blocks in (self.blocks, self.decoder_blocks):
+            for b in blocks:
+                ps += [b.norm1.weight, b.norm1.bias, b.attn.qkv.weight, b.attn.qkv.bias, b.attn.proj.weight, b.attn.proj.bias,
+                       b.norm2.weight, b.norm2.bias, b.mlp.fc1.weight, b.mlp.fc1.bias, b.mlp.fc2.weight, b.mlp.fc2.bias]
+            if blocks is self.blocks:
+                ps += [self.norm.weight, self.norm.bias, self.decoder_embed.weight, self.decoder_embed.bias, self.decoder_noise_token,
+                       self.decoder_pos_embed]
+        return ps + [self.decoder_norm.weight, self.decoder_norm.bias, self.decoder_pred.weight, self.decoder_pred.bias]
+
+    def _train_offsets(self):
+        """(0 = encoder vector | 1 = decoder vector, offset) of every _train_params() entry."""
+        out, which, off = [], 0, 0
+        for p in self._train_params():
+            if p is self.decoder_embed.weight:
+                which, off = 1, 0
+            out.append((which, off))
+            off += p.numel()
+        return out
+
     def _decoder_dims(self):
         return _capi.OsVitDims(self.img_size, self.patch_size, self.in_chans, self.decoder_embed_dim, self.decoder_depth,
                                self.decoder_num_heads, self.decoder_mlp_hidden)
@@ -149,14 +219,19 @@ class Transformer_Autoencoder(nn.Module):
         versions = tuple((p.data_ptr(), p._version) for p in self.parameters())
         if self._loaded is not None and self._loaded[0] == versions and getattr(eng, "_vit_owner", None) is self:
             return
-        flat = self._flat(dev)
+        self._load_flats_locked(eng, self._flat(dev), self._flat_decoder(dev) if self.has_decoder else None, versions)
+
+    def _load_flats_locked(self, eng, flat, dflat, versions=None):
+        """Loads these flat vectors unless they are the loaded ones (versions None: a backward's pinned weights, which the next
+        forward must not mistake for the parameters' current values)."""
+        if self._loaded is not None and self._loaded[1] is flat and self._loaded[2] is dflat and getattr(eng, "_vit_owner", None) is self:
+            return
         d = _capi.OsVitDims(self.img_size, self.patch_size, self.in_chans, self.embed_dim, self.depth, self.num_heads,
                             self.mlp_hidden)
         assert flat.numel() == eng.lib.os_vit_param_count(C.byref(d)), "flat ViT weight vector has the wrong length"
         eng._check(eng.lib.os_vit_load(eng._h, C.byref(d), _ptr(flat)), "os_vit_load")
-        dflat = None
         if self.has_decoder:
-            dflat, dd = self._flat_decoder(dev), self._decoder_dims()
+            dd = self._decoder_dims()
             assert dflat.numel() == eng.lib.os_vit_decoder_param_count(C.byref(dd), self.embed_dim), \
                 "flat ViT decoder weight vector has the wrong length"
             eng._check(eng.lib.os_vit_load_decoder(eng._h, C.byref(dd), self.embed_dim, _ptr(dflat)), "os_vit_load_decoder")
@@ -210,9 +285,12 @@ class Transformer_Autoencoder(nn.Module):
         return loss
 
     def forward(self, imgs):
-        """(loss, pred) like the reference (transformer_model.py:171-175): os_vit_encode + one os_vit_decode."""
+        """(loss, pred) like the reference (transformer_model.py:171-175): os_vit_encode + one os_vit_decode; in a trainable
+        module under enabled gradients os_vit_forward_train, with loss.backward() on os_vit_backward (pred: no gradient)."""
         self._need_decoder()
         eng = self._engine(imgs)
+        if self.trainable and torch.is_grad_enabled():
+            return _VitTrainFn.apply(imgs, self, *self._train_params())
         with eng.lock:
             lat = self._encode_locked(eng, imgs)
             pred, _, loss = self._decode_locked(eng, lat, self._frames(imgs), True, False, True)
