@@ -374,6 +374,30 @@ int os_vit_forward_train(os_ctx *ctx, int32_t N, const float *images, float *ws,
 int os_vit_backward(os_ctx *ctx, int32_t N, const float *images, const float *ws, const float *dloss, float *grad_enc,
                     float *grad_dec, void *stream);
 
+/* Optimiser step of the auto-encoder: torch.optim.AdamW (amsgrad = False, maximize = False) over the two flat vectors, fused with
+ * the re-pack of every copy of the weights that the GEMMs read.
+ * Layout: w, g, m, v of the encoder in the flat layout of os_vit_param_count, of the decoder in that of
+ * os_vit_decoder_param_count; every pointer is device memory, 16-byte aligned.  m and v start as zeros and belong to the caller.
+ * Per element, with t = step (counts from 1):
+ *     w *= 1 - lr * weight_decay                       (decayed tensors only)
+ *     m  = beta1 * m + (1 - beta1) * g
+ *     v  = beta2 * v + (1 - beta2) * g * g
+ *     w -= lr / (1 - beta1^t) * m / (sqrt(v) / sqrt(1 - beta2^t) + eps)
+ * Decayed are the tensors timm's add_weight_decay decays: every matrix (patch_embed.proj.weight, the blocks' qkv / proj / fc1 /
+ * fc2 weights, decoder_embed.weight, decoder_pred.weight), cls_token and decoder_noise_token; biases and LayerNorm affines are
+ * not.  pos_embed and decoder_pos_embed are fixed: their w, m and v are neither read nor written, whatever g holds there.
+ * Preconditions: os_vit_load and os_vit_load_decoder have run and w_enc / w_dec are the very vectors they were given -- the call
+ * rewrites the context's packed copies of them (forward and transposed order) in the same pass, so the next os_vit_encode /
+ * os_vit_decode / os_vit_forward_train / os_vit_backward on the stream sees the new weights without a reload, and os_vit_backward
+ * stops re-packing the transposed matrices until the next load.  Any other write to the vectors needs a reload as before.
+ * One launch on `stream`; no host synchronisation, and no allocation or copy after the first call for a given pair of dimensions.
+ * The same inputs give the same bits.
+ * Returns 0; -1 invalid context; -2 null or misaligned pointer, or step < 1; -4 dimensions that do not tile (cannot occur for what
+ * the loads accept); -5 nothing loaded, or w_enc / w_dec are not the loaded vectors; -10 HIP error.  os_last_error has the text. */
+int os_vit_adamw_step(os_ctx *ctx, float *w_enc, float *w_dec, const float *g_enc, const float *g_dec, float *m_enc, float *v_enc,
+                      float *m_dec, float *v_dec, float lr, float beta1, float beta2, float eps, float weight_decay, int32_t step,
+                      void *stream);
+
 /* ---- Convex-MPC ground-reaction forces ("next" row f.2): the QP the reference solves with casadi + qpOASES inside
  * predict_mpc (misc/force_controller.py:70-162 builds it, kalman_filter/kalman_filter.py:141-152 fills the parameters
  * and takes column 0 of the solution).  N = 5 horizon steps x 12 forces; per trajectory:

@@ -266,6 +266,7 @@ void os_vit_decoder_destroy(os_vit_state *v)
     os_vit_dec_state *q = v->dec;
     if (!q) return;
     if (q->wp) (void)hipFree(q->wp);
+    if (q->wpt) (void)hipFree(q->wpt);
     if (q->part) (void)hipFree(q->part);
     free(q);
     v->dec = nullptr;
@@ -341,6 +342,7 @@ int os_vit_load_decoder(os_ctx *ctx, const os_vit_dims *dec, int32_t latent_dim,
     q->d = VitDims{dec->img_size, dec->patch_size, dec->embed_dim, dec->depth, dec->num_heads, dec->mlp_hidden};
     q->latent_dim = latent_dim;
     q->w = w_flat;
+    q->wpt_valid = false;
     const size_t D = q->d.dim, L = ntok(q->d), Mh = q->d.mlp, NP = (size_t)q->d.patch * q->d.patch;
     const size_t total = (size_t)q->d.depth * (3 * D * D + D * D + 2 * Mh * D) + NP * D;
     if (os_ensure_scratch(ctx, &q->wp, &q->wp_floats, total)) return -10;

@@ -1,5 +1,5 @@
 // vit_host.hpp -- host-side state and entry points that the ViT encoder (vit_kernels.hip), decoder (vit_decoder.hip) and training
-// step (vit_train.hip) share.
+// step (vit_train.hip, vit_optim.hip) share.
 #pragma once
 #include "launch.hpp"
 
@@ -34,6 +34,8 @@ struct os_vit_dec_state {
     const float *w;          // caller-owned flat weights
     float *wp; size_t wp_floats;       // per block qkv, proj, fc1, fc2, then decoder_pred, in B-fragment order
     float *part; size_t part_floats;   // float64 loss partials
+    float *wpt; size_t wpt_floats;     // the same matrices transposed (vit_pack_wt_kernel's order), written by vit_adamw_pack_kernel
+    bool wpt_valid;                    // wpt holds the transposes of w's current values (cleared by every load)
 };
 
 struct os_vit_state {
@@ -44,6 +46,10 @@ struct os_vit_state {
     bool att_attr_set, mlp_attr_set, att_bwd_attr_set;
     os_vit_dec_state *dec;   // created by os_vit_load_decoder
     float *tbuf; size_t tbuf_floats;   // os_vit_backward's scratch (vit_train.hip)
+    float *wpt; size_t wpt_floats;     // per block qkv, proj, fc1, fc2 transposed (the patch embedding's transpose is never read)
+    bool wpt_valid;                    // as in os_vit_dec_state
+    void *opt_table; size_t opt_entries, opt_cap;   // vit_adamw_pack_kernel's work table on the device (vit_optim.hip)
+    osv::VitDims opt_enc, opt_dec; int opt_latent;  // the dimensions it was built for
 };
 
 // the context's ViT state, created empty on first use (null: out of memory, message set)

@@ -1029,6 +1029,8 @@ void os_vit_destroy(os_ctx *ctx)
     if (v->buf) (void)hipFree(v->buf);
     if (v->tbuf) (void)hipFree(v->tbuf);
     if (v->wp) (void)hipFree(v->wp);
+    if (v->wpt) (void)hipFree(v->wpt);
+    if (v->opt_table) (void)hipFree(v->opt_table);
     free(v);
     ctx->vit = nullptr;
 }
@@ -1232,6 +1234,7 @@ int os_vit_load(os_ctx *ctx, const os_vit_dims *d, const float *w_flat)
     if (!v) return -13;
     v->d = VitDims{d->img_size, d->patch_size, d->embed_dim, d->depth, d->num_heads, d->mlp_hidden};
     v->w = w_flat;
+    v->wpt_valid = false;
     // re-pack the projection matrices once (inference weights are static): [patch | per block: qkv, proj, fc1, fc2]
     const size_t D = d->embed_dim, PP = (size_t)d->patch_size * d->patch_size, L = ntok(v->d), Mh = d->mlp_hidden;
     const size_t total = D * PP + (size_t)d->depth * (3 * D * D + D * D + 2 * Mh * D);

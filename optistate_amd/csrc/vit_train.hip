@@ -12,7 +12,8 @@
 //   vit_dw_kernel          dW[n][k] = sum_m dY[m][n] X[m][k] and the bias gradient from the same pass, per M-slice partials
 //   reduce_parts_kernel    the partials summed in a fixed order: gradients are bit-reproducible
 //   ln_bwd_kernel          LayerNorm backward + the residual add of the incoming gradient; dgamma / dbeta as per-workgroup partials
-//   vit_pack_wt_kernel     W^T in B-fragment order: dX = dY . W runs on vit_gemm_kernel (EPI 7)
+//   vit_pack_wt_kernel     W^T in B-fragment order: dX = dY . W runs on vit_gemm_kernel (EPI 7); skipped for a matrix whose
+//                          resident transposed pack is current (vit_optim.hip writes those in the optimiser step)
 //   gelu_bwd_kernel, loss_grad_kernel, enc_head_bwd_kernel, dec_seed_bwd_kernel, outer_sum_kernel, fill_kernel: the two ends
 // All fp32, products on v_mfma_f32_32x32x2_f32; no atomics anywhere.
 #include "vit_host.hpp"
@@ -557,14 +558,19 @@ void weight_grad(const Bwd &b, int N, int K, const float *dY, int ldy, const flo
     reduce_parts(b.ctx, slices, n, n, b.part, grad, b.s);
 }
 
-// dXin [M][Kin] = dY [M][Nout] . W  (W [Nout][Kin] flat); with the pre-activations H of a GELU in front: * gelu'(H)
-int input_grad(const Bwd &b, int Nout, int Kin, const float *W, const float *dY, float *dXin, const float *H)
+// dXin [M][Kin] = dY [M][Nout] . W  (W [Nout][Kin] flat); with the pre-activations H of a GELU in front: * gelu'(H).
+// Wt: W's resident transposed pack (vit_adamw_pack_kernel keeps it current), or null: packed here into b.wt -- the same floats.
+int input_grad(const Bwd &b, int Nout, int Kin, const float *W, const float *Wt, const float *dY, float *dXin, const float *H)
 {
-    int slot = os_prof_begin(b.ctx, OS_PHASE_TRAIN_MISC, b.s, "vit_pack_wt_kernel");
-    hipLaunchKernelGGL(vit_pack_wt_kernel, dim3(256), dim3(256), 0, b.s, Kin, Nout, W, b.wt);
-    os_prof_end(b.ctx, slot, b.s);
+    int slot;
+    if (!Wt) {
+        slot = os_prof_begin(b.ctx, OS_PHASE_TRAIN_MISC, b.s, "vit_pack_wt_kernel");
+        hipLaunchKernelGGL(vit_pack_wt_kernel, dim3(256), dim3(256), 0, b.s, Kin, Nout, W, b.wt);
+        os_prof_end(b.ctx, slot, b.s);
+        Wt = b.wt;
+    }
     GemmArgs g;
-    g.M = b.M; g.N = Kin; g.K = Nout; g.lda = Nout; g.A = dY; g.img = nullptr; g.img_size = g.grid = g.patch = 0; g.Wp = b.wt;
+    g.M = b.M; g.N = Kin; g.K = Nout; g.lda = Nout; g.A = dY; g.img = nullptr; g.img_size = g.grid = g.patch = 0; g.Wp = Wt;
     g.bias = nullptr; g.C = dXin; g.pos = nullptr; g.L = 0; g.R = nullptr; g.C2 = nullptr;
     if (int rc = os_vit_launch_gemm(b.ctx, 0, 7, g, b.s, "vit_gemm_kernel<dX>")) return rc;
     if (H) {
@@ -617,8 +623,8 @@ int blocks_forward(os_ctx *ctx, os_vit_state *v, const VitDims &d, const float *
 }
 
 // backward of the blocks of d, last to first: b.dX holds the gradient of the last block's output on entry and of block 0's input
-// on return.  w / ws / grad at block 0.
-int blocks_backward(const Bwd &b, const VitDims &d, const float *w, const float *ws, float *grad, int N)
+// on return.  w / ws / grad at block 0; wtr: the stack's resident transposed packs (per block qkv, proj, fc1, fc2) or null.
+int blocks_backward(const Bwd &b, const VitDims &d, const float *w, const float *wtr, const float *ws, float *grad, int N)
 {
     const int D = d.dim, Mh = d.mlp;
     const BlockOff o = block_off(d);
@@ -633,22 +639,25 @@ int blocks_backward(const Bwd &b, const VitDims &d, const float *w, const float 
     for (int blk = d.depth - 1; blk >= 0; blk--) {
         const float *wb = w + blk * o.total, *a = ws + blk * k.total;
         float *gb = grad + blk * o.total;
+        const size_t DD = (size_t)D * D, MD = (size_t)Mh * D;
+        const float *tq = wtr ? wtr + blk * (4 * DD + 2 * MD) : nullptr, *tp = wtr ? tq + 3 * DD : nullptr;
+        const float *t1 = wtr ? tp + DD : nullptr, *t2 = wtr ? t1 + MD : nullptr;
         // x_out = x_mid + fc2(gelu(fc1(LN2(x_mid))))
         weight_grad(b, D, Mh, b.dX, D, a + k.g, nullptr, nullptr, gb + o.fc2w);
-        if (int rc = input_grad(b, D, Mh, wb + o.fc2w, b.dX, b.dBig, a + k.h)) return rc;
+        if (int rc = input_grad(b, D, Mh, wb + o.fc2w, t2, b.dX, b.dBig, a + k.h)) return rc;
         os_vit_launch_layernorm(b.ctx, b.M, D, a + k.xmid, wb + o.ln2, wb + o.ln2 + D, b.Yn, b.s);
         weight_grad(b, Mh, D, b.dBig, Mh, b.Yn, nullptr, nullptr, gb + o.fc1w);
-        if (int rc = input_grad(b, Mh, D, wb + o.fc1w, b.dBig, b.dT, nullptr)) return rc;
+        if (int rc = input_grad(b, Mh, D, wb + o.fc1w, t1, b.dBig, b.dT, nullptr)) return rc;
         ln_grad(b, D, a + k.xmid, b.dT, wb + o.ln2, b.dX, b.dX, gb + o.ln2);
         // x_mid = x_in + proj(attention(qkv(LN1(x_in))))
         weight_grad(b, D, D, b.dX, D, a + k.ao, nullptr, nullptr, gb + o.projw);
-        if (int rc = input_grad(b, D, D, wb + o.projw, b.dX, b.dT, nullptr)) return rc;
+        if (int rc = input_grad(b, D, D, wb + o.projw, tp, b.dX, b.dT, nullptr)) return rc;
         const int slot = os_prof_begin(b.ctx, OS_PHASE_VIT_ATTN, b.s, "attention_bwd_kernel");
         hipLaunchKernelGGL(attention_bwd_kernel, dim3(N * d.heads), dim3(512), alds, b.s, L, D, d.heads, a + k.qkv, a + k.ao, b.dT, b.dBig);
         os_prof_end(b.ctx, slot, b.s);
         os_vit_launch_layernorm(b.ctx, b.M, D, a + k.xin, wb + o.ln1, wb + o.ln1 + D, b.Yn, b.s);
         weight_grad(b, 3 * D, D, b.dBig, 3 * D, b.Yn, nullptr, nullptr, gb + o.qkvw);
-        if (int rc = input_grad(b, 3 * D, D, wb + o.qkvw, b.dBig, b.dT, nullptr)) return rc;
+        if (int rc = input_grad(b, 3 * D, D, wb + o.qkvw, tq, b.dBig, b.dT, nullptr)) return rc;
         ln_grad(b, D, a + k.xin, b.dT, wb + o.ln1, b.dX, b.dX, gb + o.ln1);
         OS_HIP(b.ctx, hipGetLastError());
     }
@@ -741,9 +750,11 @@ int os_vit_backward(os_ctx *ctx, int32_t N, const float *images, const float *ws
     os_prof_end(ctx, slot, s);
     os_vit_launch_layernorm(ctx, M, Dd, xd_out, wd + o_dnorm, wd + o_dnorm + Dd, b.Yn, s);
     weight_grad(b, NP, Dd, dpred, NP, b.Yn, nullptr, nullptr, grad_dec + o_pred);
-    if (int rc = input_grad(b, NP, Dd, wd + o_pred, dpred, b.dT, nullptr)) return rc;
+    const float *wtd = q->wpt_valid ? q->wpt : nullptr, *wte = v->wpt_valid ? v->wpt : nullptr;
+    const float *wtpred = wtd ? wtd + (size_t)dd.depth * (4 * (size_t)Dd * Dd + 2 * (size_t)dd.mlp * Dd) : nullptr;
+    if (int rc = input_grad(b, NP, Dd, wd + o_pred, wtpred, dpred, b.dT, nullptr)) return rc;
     ln_grad(b, Dd, xd_out, b.dT, wd + o_dnorm, nullptr, b.dX, grad_dec + o_dnorm);
-    if (int rc = blocks_backward(b, dd, wd + o_dblk, ws + t.dec, grad_dec + o_dblk, N)) return rc;
+    if (int rc = blocks_backward(b, dd, wd + o_dblk, wtd, ws + t.dec, grad_dec + o_dblk, N)) return rc;
     // the token matrix: decoder_embed (row 0 of every image), the noise token (the other rows), no gradient for the position table
     slot = os_prof_begin(ctx, OS_PHASE_TRAIN_MISC, s, "dec_seed_bwd_kernel");
     hipLaunchKernelGGL(dec_seed_bwd_kernel, dim3(N), dim3(256), 0, s, L, Dd, D, wd, b.dX, b.part, dlat);
@@ -764,7 +775,7 @@ int os_vit_backward(os_ctx *ctx, int32_t N, const float *images, const float *ws
     hipLaunchKernelGGL(enc_head_bwd_kernel, dim3((N + 3) / 4), dim3(256), 0, s, N, L, D, xe_out, we + o_norm, ws + t.lat, dlat, b.dX, b.part);
     os_prof_end(ctx, slot, s);
     reduce_parts(ctx, N, (size_t)2 * D, (size_t)2 * D, b.part, grad_enc + o_norm, s);
-    if (int rc = blocks_backward(b, e, we + o_blk, ws + t.enc, grad_enc + o_blk, N)) return rc;
+    if (int rc = blocks_backward(b, e, we + o_blk, wte, ws + t.enc, grad_enc + o_blk, N)) return rc;
     reduce_parts(ctx, N, D, (size_t)L * D, b.dX, grad_enc + o_cls, s);
     weight_grad(b, D, PP, b.dX, D, nullptr, images, &e, grad_enc);
     fill(ctx, grad_enc + o_pos, (size_t)L * D, s);

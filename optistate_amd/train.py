@@ -8,6 +8,9 @@
   (`torch.distributed`, backend "nccl"), then identical fused-Adam updates.  The bucket is latency-bound at 1.69 MB, so
   there is no bucketing/overlap machinery.  The target of gru_train.py:237-244 is built on the
   device (no host round trip, no per-sample Python loop).
+* `VitTrainer`: the auto-encoder's loop (reference transformer/autoencoder_training.py:83-114) with the weights resident: forward,
+  backward and ONE AdamW launch that also re-packs what the GEMMs read (os_vit_adamw_step); `add_weight_decay` restates timm's
+  grouping rule of the same name for callers who drive torch.optim.AdamW themselves.
 """
 import os
 
@@ -308,3 +311,95 @@ class DataParallelTrainer:
     def replica_divergence(self):
         """max over ranks of |w_r - w_0| (0.0 = the replicas are still identical)."""
         return replica_divergence(self.bucket.w, self.group)
+
+
+def decay_partition(named_parameters):
+    """timm's optim_factory.add_weight_decay rule on (name, parameter) pairs: -> (decayed names, undecayed names).  A parameter is
+    NOT decayed when it is one-dimensional or its name ends in ".bias"; everything else is, cls_token and decoder_noise_token of
+    shape (1, 1, D) included.  Frozen parameters (requires_grad False: the position tables) are in neither list."""
+    decay, no_decay = [], []
+    for name, p in named_parameters:
+        if not p.requires_grad:
+            continue
+        (no_decay if p.dim() == 1 or name.endswith(".bias") else decay).append(name)
+    return decay, no_decay
+
+
+def add_weight_decay(model, weight_decay=1e-5):
+    """The parameter groups that the reference hands to torch.optim.AdamW (autoencoder_training.py:94-96), by decay_partition."""
+    named = dict(model.named_parameters())
+    decay, no_decay = decay_partition(named.items())
+    return [{"params": [named[k] for k in no_decay], "weight_decay": 0.0},
+            {"params": [named[k] for k in decay], "weight_decay": weight_decay}]
+
+
+class VitTrainer:
+    """One optimisation step of `Transformer_Autoencoder(decoder=True)` = os_vit_forward_train, os_vit_backward (dloss = 1),
+    os_vit_adamw_step, all on the engine's stream under its lock: no autograd, no host synchronisation, and after the first step at a
+    batch size no allocation.  The model's weights live in ONE buffer [encoder | decoder] in the library's flat order, gradients
+    (`g`, laid out the same way: a data-parallel step can all-reduce it as it stands) and AdamW's `m`, `v` in three more; every
+    parameter's `.data` is a view of the first and `.grad` a view of the second, so `model.state_dict()` still writes a reference
+    checkpoint and `model.forward_encoder / forward / reconstruct` under no_grad run on the resident weights without a reload.
+    Decay groups: decay_partition.  `lr` is read at every step.
+    A write through torch that moves a parameter's version counter (`model.load_state_dict`, `p.copy_` under no_grad) is seen by
+    the next step, which packs the weights again once; a write that bypasses the counters (`p.data.copy_`) needs invalidate()."""
+
+    def __init__(self, model, lr=4e-4, betas=(0.9, 0.95), eps=1e-8, weight_decay=1e-3):
+        from .engine import default_engine
+        if not getattr(model, "has_decoder", False):
+            raise ValueError("VitTrainer needs Transformer_Autoencoder(decoder=True): the loss is the decoder's")
+        params, offsets = model._train_params(), model._train_offsets()
+        dev = params[0].device
+        if dev.type != "cuda" or any(p.device != dev or p.dtype != torch.float32 for p in params):
+            raise RuntimeError("VitTrainer needs the float32 model on the MI355X (no CPU fallback)")
+        self.model, self.eng = model, default_engine(dev.index or 0)
+        self.lr, self.betas, self.eps, self.weight_decay, self.t = lr, betas, eps, weight_decay, 0
+        n_enc = sum(p.numel() for p, (which, _) in zip(params, offsets) if which == 0)
+        n = sum(p.numel() for p in params)
+        self._w, self._g = torch.empty(n, dtype=torch.float32, device=dev), torch.zeros(n, dtype=torch.float32, device=dev)
+        self._m, self._v = torch.zeros_like(self._g), torch.zeros_like(self._g)
+        split = lambda t: (t[:n_enc], t[n_enc:])
+        self.w, self.g, self.m, self.v = split(self._w), split(self._g), split(self._m), split(self._v)
+        for p, (which, off) in zip(params, offsets):
+            k = p.numel()
+            self.w[which][off:off + k].copy_(p.detach().reshape(-1))
+            p.data = self.w[which][off:off + k].view_as(p)
+            if p.requires_grad:
+                p.grad = self.g[which][off:off + k].view_as(p)
+        self._one = torch.ones((), dtype=torch.float32, device=dev)
+        self._ws = {}                                       # N -> (workspace, loss)
+        model._adopted = self.w
+        with self.eng.lock:
+            model._loaded = None
+            model._load_locked(self.eng, dev)
+
+    def invalidate(self):
+        """The flat weights were written behind torch's version counters: the next step packs them again."""
+        self.model._loaded = None
+
+    def step(self, imgs):
+        """imgs (N, 1, H, W) or (N, H, W) on the GPU -> the loss of this step's forward, a 0-d device tensor.  It is the trainer's
+        buffer for this N: the next step at the same N overwrites it (clone() to keep it)."""
+        from .engine import _ptr
+        m, e = self.model, self.eng
+        if not imgs.is_cuda:
+            raise RuntimeError("VitTrainer.step needs the images on the MI355X (no CPU fallback)")
+        img = m._frames(imgs.detach())
+        N = img.shape[0]
+        with e.lock:
+            m._load_locked(e, img.device)                   # a no-op unless torch wrote the parameters or another model took the context
+            if N not in self._ws:
+                nws = e.lib.os_vit_train_ws_floats(e._h, N)
+                if nws == 0:
+                    raise RuntimeError(f"os_vit_train_ws_floats: {e.lib.os_last_error(e._h).decode()}")
+                self._ws[N] = (torch.empty(nws, dtype=torch.float32, device=img.device), torch.empty((), dtype=torch.float32, device=img.device))
+            ws, loss = self._ws[N]
+            s = e._stream()
+            e._check(e.lib.os_vit_forward_train(e._h, N, _ptr(img), _ptr(ws), None, _ptr(loss), s), "os_vit_forward_train")
+            e._check(e.lib.os_vit_backward(e._h, N, _ptr(img), _ptr(ws), _ptr(self._one), _ptr(self.g[0]), _ptr(self.g[1]), s),
+                     "os_vit_backward")
+            e._check(e.lib.os_vit_adamw_step(e._h, _ptr(self.w[0]), _ptr(self.w[1]), _ptr(self.g[0]), _ptr(self.g[1]), _ptr(self.m[0]),
+                                             _ptr(self.v[0]), _ptr(self.m[1]), _ptr(self.v[1]), self.lr, self.betas[0], self.betas[1],
+                                             self.eps, self.weight_decay, self.t + 1, s), "os_vit_adamw_step")
+            self.t += 1
+        return loss

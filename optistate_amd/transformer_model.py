@@ -158,8 +158,21 @@ class Transformer_Autoencoder(nn.Module):
                 if m.bias is not None:
                     nn.init.constant_(m.bias, 0)
         self._loaded = None
+        self._adopted = None       # (encoder, decoder) flat vectors of a VitTrainer: the parameters are views of them
+
+    def _adopted_flats(self):
+        """The trainer's vectors while the parameters still are views of them; model.to(...), load_state_dict(assign=True) and
+        the like rebind the parameters, and the adoption ends there: the module concatenates again (its trainer's next step then
+        fails with -5, its vectors no longer being the loaded ones)."""
+        a = self._adopted
+        if a is not None and any(p.data_ptr() != a[which].data_ptr() + 4 * off
+                                 for p, (which, off) in zip(self._train_params(), self._train_offsets())):
+            a = self._adopted = None
+        return a
 
     def _flat(self, dev):
+        if self._adopted_flats() is not None:
+            return self._adopted[0]
         sd = self.state_dict()
         parts = [sd["patch_embed.proj.weight"].reshape(-1), sd["patch_embed.proj.bias"], sd["cls_token"].reshape(-1),
                  sd["pos_embed"].reshape(-1)]
@@ -170,6 +183,8 @@ class Transformer_Autoencoder(nn.Module):
 
     def _flat_decoder(self, dev):
         """include/optistate_hip.h (os_vit_load_decoder): the decoder's flat weight vector."""
+        if self._adopted_flats() is not None:
+            return self._adopted[1]
         sd = self.state_dict()
         parts = [sd["decoder_embed.weight"], sd["decoder_embed.bias"], sd["decoder_noise_token"], sd["decoder_pos_embed"]]
         for i in range(self.decoder_depth):
@@ -219,6 +234,8 @@ class Transformer_Autoencoder(nn.Module):
         versions = tuple((p.data_ptr(), p._version) for p in self.parameters())
         if self._loaded is not None and self._loaded[0] == versions and getattr(eng, "_vit_owner", None) is self:
             return
+        if self._adopted_flats() is not None:
+            self._loaded = None    # the same vectors with other contents (a write through torch): pack them again
         self._load_flats_locked(eng, self._flat(dev), self._flat_decoder(dev) if self.has_decoder else None, versions)
 
     def _load_flats_locked(self, eng, flat, dflat, versions=None):
