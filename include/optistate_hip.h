@@ -336,6 +336,29 @@ size_t os_vit_param_count(const os_vit_dims *d);
 int os_vit_load(os_ctx *ctx, const os_vit_dims *d, const float *w_flat);
 int os_vit_encode(os_ctx *ctx, int32_t N, const float *images, float *latent, void *stream);
 
+/* Frame ingest: what every path into the ViT does to a depth frame first -- `Resize((224, 224)) -> Grayscale(1) -> ToTensor()` on a
+ * PIL image after `convert('RGB')` (gru/gru_test.py:49-53,122-124, gru/gru_train.py:137-165, transformer/autoencoder_load.py:32-53,
+ * transformer/autoencoder_training.py:42-44,67-69) -- on the device, BIT FOR BIT as Pillow computes it (integer arithmetic: a
+ * horizontal bilinear pass in 22-bit fixed point rounded to uint8, a vertical one on those bytes, L = (19595 R + 38470 G + 7471 B +
+ * 32768) >> 16, then float(L) / 255 correctly rounded; an axis whose length already is out_size passes through).
+ * frames [N][H][W][C] uint8, C = 1 (an 'L' image) or 3 (RGB); out [N][out_size][out_size] float32 in [0, 1].
+ * One launch; the coefficient tables of a geometry (H, W, C, out_size) are built and uploaded the first time it is seen (four
+ * geometries are cached per context, the least recently used is replaced) -- later calls allocate nothing, copy nothing and do not
+ * synchronise.  Served: H, W <= 8192 at any per-axis down-scale ratio up to 32, any up-scale, out_size <= 8192, and whatever else
+ * fits the kernel's LDS window; beyond that -4 with the limit in os_last_error (never a wrong image).  N < 1, C outside {1, 3},
+ * null pointers: -2.
+ * os_vit_encode_frames (the loop of gru/gru_train.py:157-172 and gru/gru_test.py:119-132, batched): os_frames_ingest with out_size
+ * = the loaded encoder's img_size into a context-owned buffer (grown on first use), then os_vit_encode on it: the latent is
+ * bit-identical to the two calls made separately.
+ * os_frames_plan_info: the plan of a geometry (built if new) for reports -- info[8] (host) = tile rows, tile columns, LDS bytes per
+ * workgroup, window rows per stage-A/B chunk, the largest tile window's rows, its bytes per row, the bytes stage A reads per image
+ * (16-byte pieces over all tiles, halos included), tiles per image. */
+int os_frames_ingest(os_ctx *ctx, int32_t N, const uint8_t *frames, int32_t H, int32_t W, int32_t C, int32_t out_size,
+                     float *out /* [N][out_size][out_size] */, void *stream);
+int os_vit_encode_frames(os_ctx *ctx, int32_t N, const uint8_t *frames, int32_t H, int32_t W, int32_t C, float *latent /* [N][D] */,
+                         void *stream);
+int os_frames_plan_info(os_ctx *ctx, int32_t H, int32_t W, int32_t C, int32_t out_size, int64_t *info /* host [8] */);
+
 /* Decoder half of the same class (transformer/transformer_model.py:137-175: forward_decoder, forward_loss, unpatchify).
  * `dec` carries img_size, patch_size, in_chans, embed_dim = decoder_embed_dim, depth = decoder_depth, num_heads =
  * decoder_num_heads, mlp_hidden; latent_dim is the encoder's embed_dim.  With Dd = decoder_embed_dim, L = 1 + (img/patch)^2 and

@@ -42,6 +42,7 @@ EXPORTS = [
     "os_gru_get_stack", "os_fused_set_tile", "os_stack_check", "os_kf_step_mpc",
     "os_vit_decoder_param_count", "os_vit_load_decoder", "os_vit_decode", "os_vit_recon_loss",
     "os_vit_train_ws_floats", "os_vit_forward_train", "os_vit_backward", "os_vit_adamw_step",
+    "os_frames_ingest", "os_vit_encode_frames", "os_frames_plan_info",
 ]
 
 
@@ -152,6 +153,11 @@ def load():
     lib.os_vit_backward.restype = C.c_int
     lib.os_vit_adamw_step.argtypes = [vp] + [f32p] * 8 + [C.c_float] * 5 + [i32, vp]
     lib.os_vit_adamw_step.restype = C.c_int
+    lib.os_frames_ingest.argtypes = [vp, i32, vp, i32, i32, i32, i32, f32p, vp]
+    lib.os_vit_encode_frames.argtypes = [vp, i32, vp, i32, i32, i32, f32p, vp]
+    lib.os_frames_plan_info.argtypes = [vp, i32, i32, i32, i32, C.POINTER(C.c_int64)]
+    for n in ("os_frames_ingest", "os_vit_encode_frames", "os_frames_plan_info"):
+        getattr(lib, n).restype = C.c_int
     lib.os_mpc_set_weights.argtypes = [vp, C.POINTER(C.c_double), C.c_double, C.c_double, C.c_double]
     lib.os_mpc_solve.argtypes = [vp, i32, f32p, f32p, f32p, vp, f32p, f32p, vp, vp, i32, vp]
     lib.os_kf_mpc_run.argtypes = [vp, i32, i32, f32p, f32p, f32p, vp, f32p, f32p, f32p, f32p, f32p, f32p, f32p, f32p, vp, vp, u32, vp]

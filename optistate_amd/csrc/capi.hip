@@ -70,6 +70,8 @@ int os_create(const os_kf_config *cfg, os_ctx **out)
         e = getenv("OS_VIT_ATT_DMA"); c->tune_vit_att_dma = e ? atoi(e) : 1;
         e = getenv("OS_VIT_MLP_BM"); c->tune_vit_mlp_bm = e ? atoi(e) : 64;
         e = getenv("OS_GRU_WIDE"); c->tune_gru_wide = e ? atoi(e) : 1; c->wide_attr_set = false;
+        // frame ingest: LDS (KB) a tile should stay within; measured at 1,024 x 480 x 640 x 3 -> 224: 24 (16 x 32 tiles) 0.50 ms, 40 (16 x 64) 0.72, 64 (32 x 64) 1.08
+        e = getenv("OS_FRAMES_LDS_KB"); c->tune_frames_lds_kb = e && atoi(e) >= 8 && atoi(e) <= 64 ? atoi(e) : 24;
         e = getenv("OS_SWEEP_WR"); c->tune_sweep_wr = e ? atoi(e) : 32;
         e = getenv("OS_SWEEP_NW"); c->tune_sweep_nw = e ? atoi(e) : 0;
         // weight-gradient kernels on a side stream underneath the next layer's sweep: unset = where CUs are idle and the launches are long
@@ -114,6 +116,7 @@ void os_destroy(os_ctx *ctx)
     os_train_destroy(ctx);
     os_step_destroy(ctx);
     os_vit_destroy(ctx);
+    os_frames_destroy(ctx);
     for (auto &sl : ctx->gru_slots)
     {
         if (sl.packed) (void)hipFree(sl.packed);

@@ -100,6 +100,8 @@ struct os_ctx {
     float *mpc_scratch; size_t mpc_scratch_floats;
     bool fused_attr_set, sweep_attr_set, layer_attr_set, split_attr_set, ahead_attr_set, stage_attr_set, stack_attr_set;  // hipFuncSetAttribute(MaxDynamicSharedMemorySize) done on this device
     void *vit;                           // os_vit_state (vit_kernels.hip), created by os_vit_load
+    void *frames;                        // osfr::State (frames_kernels.hip): the frame-ingest plans per geometry, created on first use
+    int tune_frames_lds_kb;              // OS_FRAMES_LDS_KB: LDS per workgroup that the ingest plan prefers when it picks a tile (the hard limit is 64)
     void *train;                         // os_train_state (gru_train_kernels.hip), created on first use
     int bwd_mark_layer; void *bwd_mark_event;   // os_gru_backward_mark: event recorded behind this layer's weight-gradient kernel
     void *step;                          // os_step_state (kf_step.hip): pinned, device-mapped staging block of os_kf_step
@@ -188,3 +190,4 @@ int os_gru_launch_wide(os_ctx *ctx, osg::WideArgs &a, bool save, hipStream_t s);
 void os_train_destroy(os_ctx *ctx);
 void os_step_destroy(os_ctx *ctx);
 void os_vit_destroy(os_ctx *ctx);
+void os_frames_destroy(os_ctx *ctx);

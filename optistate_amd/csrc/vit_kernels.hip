@@ -623,6 +623,16 @@ __global__ __launch_bounds__(256, 2) void vit_gemm_kernel(const GemmArgs a)
 // immediately consumed as a K-slice of fc2, whose 128 x 128 accumulators stay in registers across the slices.  Eight waves:
 // wave = (32-column chunk w & 3, row-block pair w >> 2); per slice 128 + 128 MFMAs per wave, two barriers.
 // embed_dim = 128 only (one K-chunk of input, four output chunks); LDS: input tile 64 KB + hidden slice 64 KB.
+// Sum of the eight per-slot partial sums of a LayerNorm quarter row as a balanced tree.  A thread holds its eight 16-byte slots in
+// STORED order, and stored slot j is source slot j ^ (row & 7) with `row` counted inside the tile: a running sum over j adds a row's
+// columns in an order that depends on where the row sits in its tile, and an image then gets other last bits when its tokens start
+// at another row of the token matrix (a batch cut into chunks against the whole batch).  An XOR of the index maps the pairs, the
+// pairs of pairs and the halves of this tree onto one another, and the additions commute: the sum is the same for every row & 7.
+__device__ __forceinline__ float xor_tree_sum8(const float (&p)[8])
+{
+    return ((p[0] + p[1]) + (p[2] + p[3])) + ((p[4] + p[5]) + (p[6] + p[7]));
+}
+
 struct MlpArgs {
     size_t M;
     int Mh;                     // hidden width, a multiple of 128
@@ -759,17 +769,18 @@ __device__ __forceinline__ void vit_mlp_tile(const MlpArgs &a, const size_t row0
         const int row = threadIdx.x >> 2, qd = threadIdx.x & 3;
         float *rp = As + row * D + qd * 32;
         float4 v4[8];
-        float sum = 0.f;
+        float ps[8];
 #pragma unroll
-        for (int j = 0; j < 8; j++) { v4[j] = *reinterpret_cast<const float4 *>(rp + 4 * j); sum += (v4[j].x + v4[j].y) + (v4[j].z + v4[j].w); }
+        for (int j = 0; j < 8; j++) { v4[j] = *reinterpret_cast<const float4 *>(rp + 4 * j); ps[j] = (v4[j].x + v4[j].y) + (v4[j].z + v4[j].w); }
+        float sum = xor_tree_sum8(ps);
         sum += dpp_mov<0xB1>(sum); sum += dpp_mov<0x4E>(sum);
         const float mean = sum * (1.0f / D);
-        float q = 0.f;
 #pragma unroll
         for (int j = 0; j < 8; j++) {
             v4[j].x -= mean; v4[j].y -= mean; v4[j].z -= mean; v4[j].w -= mean;
-            q += (v4[j].x * v4[j].x + v4[j].y * v4[j].y) + (v4[j].z * v4[j].z + v4[j].w * v4[j].w);
+            ps[j] = (v4[j].x * v4[j].x + v4[j].y * v4[j].y) + (v4[j].z * v4[j].z + v4[j].w * v4[j].w);
         }
+        float q = xor_tree_sum8(ps);
         q += dpp_mov<0xB1>(q); q += dpp_mov<0x4E>(q);
         const float rstd = rsqrtf(q * (1.0f / D) + 1e-5f);
 #pragma unroll
@@ -889,17 +900,18 @@ __device__ __forceinline__ void vit_mlp_tile(const MlpArgs &a, const size_t row0
         const int row = threadIdx.x >> 2, qd = threadIdx.x & 3;
         const float *rp = As + row * D + qd * 32;
         float4 v4[8];
-        float sum = 0.f;
+        float ps[8];
 #pragma unroll
-        for (int j = 0; j < 8; j++) { v4[j] = *reinterpret_cast<const float4 *>(rp + 4 * j); sum += (v4[j].x + v4[j].y) + (v4[j].z + v4[j].w); }
+        for (int j = 0; j < 8; j++) { v4[j] = *reinterpret_cast<const float4 *>(rp + 4 * j); ps[j] = (v4[j].x + v4[j].y) + (v4[j].z + v4[j].w); }
+        float sum = xor_tree_sum8(ps);
         sum += dpp_mov<0xB1>(sum); sum += dpp_mov<0x4E>(sum);
         const float mean = sum * (1.0f / D);
-        float q = 0.f;
 #pragma unroll
         for (int j = 0; j < 8; j++) {
             v4[j].x -= mean; v4[j].y -= mean; v4[j].z -= mean; v4[j].w -= mean;
-            q += (v4[j].x * v4[j].x + v4[j].y * v4[j].y) + (v4[j].z * v4[j].z + v4[j].w * v4[j].w);
+            ps[j] = (v4[j].x * v4[j].x + v4[j].y * v4[j].y) + (v4[j].z * v4[j].z + v4[j].w * v4[j].w);
         }
+        float q = xor_tree_sum8(ps);
         q += dpp_mov<0xB1>(q); q += dpp_mov<0x4E>(q);
         const float rstd = rsqrtf(q * (1.0f / D) + 1e-5f);
         if (a.Wqp || (row < nrows && row0 + row < a.M)) {

@@ -210,6 +210,42 @@ class Engine:
                     "os_unpack_stream")
         return out
 
+    # ---- frame ingest (the ViT chain's Resize -> Grayscale -> ToTensor) ----
+    def _frames_u8(self, frames):
+        """uint8 frames (N,H,W,3) | (N,H,W,1) | (N,H,W), a device tensor or a numpy array (copied over) -> (tensor, N, H, W, C).
+        Anything that is not uint8 or not contiguous raises: there is no silent conversion."""
+        if isinstance(frames, np.ndarray):
+            if frames.dtype != np.uint8:
+                raise TypeError(f"optistate_amd: uint8 frames expected, got {frames.dtype}")
+            frames = torch.from_numpy(np.ascontiguousarray(frames)).to(self.device)
+        if not torch.is_tensor(frames) or frames.dtype != torch.uint8:
+            raise TypeError(f"optistate_amd: uint8 frames expected, got {getattr(frames, 'dtype', type(frames))}")
+        if not frames.is_cuda:
+            raise TypeError("optistate_amd: a device tensor (or a numpy array) is required; the hot path has no CPU fallback")
+        if not frames.is_contiguous():
+            raise ValueError("optistate_amd: contiguous frames are required (call .contiguous())")
+        if frames.dim() not in (3, 4) or (frames.dim() == 4 and frames.shape[3] not in (1, 3)):
+            raise ValueError(f"optistate_amd: frames of shape (N,H,W,3), (N,H,W,1) or (N,H,W) expected, got {tuple(frames.shape)}")
+        N, H, W = frames.shape[:3]
+        return frames, N, H, W, (frames.shape[3] if frames.dim() == 4 else 1)
+
+    def ingest_frames(self, frames, size=224):
+        """Resize((size, size)) -> Grayscale(1) -> ToTensor() of the reference's loaders (gru/gru_test.py:49-53), batched and bit for
+        bit as Pillow computes it (os_frames_ingest): uint8 frames -> float32 (N, size, size) in [0, 1]."""
+        fr, N, H, W, Cn = self._frames_u8(frames)
+        out = torch.empty((N, size, size), dtype=torch.float32, device=self.device)
+        self._check(self.lib.os_frames_ingest(self._h, N, C.c_void_p(fr.data_ptr()), H, W, Cn, int(size), _ptr(out), self._stream()),
+                    "os_frames_ingest")
+        return out
+
+    def frames_plan_info(self, H, W, channels, size=224):
+        """The ingest plan of a geometry (os_frames_plan_info) as a dict, for reports."""
+        info = (C.c_int64 * 8)()
+        self._check(self.lib.os_frames_plan_info(self._h, H, W, channels, int(size), info), "os_frames_plan_info")
+        keys = ("tile_rows", "tile_cols", "lds_bytes", "rows_per_chunk", "window_rows", "window_row_bytes", "read_bytes_per_image",
+                "tiles_per_image")
+        return dict(zip(keys, (int(v) for v in info)))
+
     def pack_contact(self, c_bt4):
         """uint8 [B][T][4] -> packed uint32-as-4-bytes [T][B]."""
         c = torch.as_tensor(c_bt4).to(self.device, dtype=torch.uint8).contiguous()

@@ -8,6 +8,7 @@ gru_train.py:59-62 (dataset min/max)                             fit_minmax()
 gru_test.py:99-101 (normalise)                                   normalize()
 gru_train.py:186-192 / gru_test.py:138-145 (windows + labels)    make_windows()
 gru_test.py:174-213 (inference loop, error bands, de-normalise)  predict_windows()
+gru_train.py:157-172 / gru_test.py:119-132 (frames -> latents)   latents_from_frames()
 
 Only data movement and dataset statistics run as torch ops; the filter and the GRU run in the HIP kernels.
 """
@@ -103,6 +104,14 @@ def make_windows(rows_norm, labels_norm, seq_len):
     window i = rows i..i+seq-1 and label i = labels[i+seq-1] (gru_train.py:186-192)."""
     w = rows_norm.unfold(0, seq_len, 1).permute(0, 2, 1).contiguous()
     return w, labels_norm[seq_len - 1:]
+
+
+def latents_from_frames(model, frames, chunk=1024):
+    """The frame loop of gru/gru_train.py:157-172 and gru/gru_test.py:119-132 (open, transform, forward_encoder, one frame at a
+    time) in chunks of `chunk` frames: uint8 frames (n,H,W[,C]) -> latents [n][embed_dim] on the device (model.encode_frames)."""
+    n = frames.shape[0]
+    parts = [model.encode_frames(frames[i:i + chunk])[:, 0] for i in range(0, n, chunk)]
+    return parts[0] if len(parts) == 1 else torch.cat(parts, dim=0)
 
 
 def predict_rows(model, rows_norm, seq_len, min_v, max_v):

@@ -230,6 +230,23 @@ class Transformer_Autoencoder(nn.Module):
         with eng.lock:                                     # load + encode as one unit: a context holds ONE auto-encoder
             return self._encode_locked(eng, x)
 
+    def preprocess(self, frames):
+        """uint8 frames (N,H,W,3) | (N,H,W,1) | (N,H,W) on the device (or a numpy array) -> (N,1,img_size,img_size) float32: the
+        reference's `transform(img).unsqueeze(0)` (gru/gru_test.py:49-53,122-124), batched, bit for bit (Engine.ingest_frames)."""
+        eng = default_engine(frames.device.index or 0) if torch.is_tensor(frames) and frames.is_cuda else default_engine(0)
+        return eng.ingest_frames(frames, self.img_size).unsqueeze(1)
+
+    def encode_frames(self, frames):
+        """forward_encoder(preprocess(frames)) in one call (os_vit_encode_frames): (N,1,embed_dim), the same bits."""
+        eng = default_engine(frames.device.index or 0) if torch.is_tensor(frames) and frames.is_cuda else default_engine(0)
+        fr, N, H, W, Cn = eng._frames_u8(frames)
+        with eng.lock:                                     # load + encode as one unit: a context holds ONE auto-encoder
+            self._load_locked(eng, fr.device)
+            lat = torch.empty((N, self.embed_dim), dtype=torch.float32, device=fr.device)
+            eng._check(eng.lib.os_vit_encode_frames(eng._h, N, C.c_void_p(fr.data_ptr()), H, W, Cn, _ptr(lat), eng._stream()),
+                       "os_vit_encode_frames")
+        return lat.reshape(N, 1, self.embed_dim)
+
     def _load_locked(self, eng, dev):
         versions = tuple((p.data_ptr(), p._version) for p in self.parameters())
         if self._loaded is not None and self._loaded[0] == versions and getattr(eng, "_vit_owner", None) is self:
