@@ -359,6 +359,30 @@ int os_vit_encode_frames(os_ctx *ctx, int32_t N, const uint8_t *frames, int32_t 
                          void *stream);
 int os_frames_plan_info(os_ctx *ctx, int32_t H, int32_t W, int32_t C, int32_t out_size, int64_t *info /* host [8] */);
 
+/* Frame augmentation: the random transforms of the auto-encoder's training chain between Grayscale and ToTensor
+ * (transformer/autoencoder_training.py:45-52) on the device, per image, BIT FOR BIT as Pillow computes them with nearest-neighbour
+ * rotation and perspective, a bilinear crop-resize and fill 0.  The randomness stays on the host: every image has an explicit
+ * record.
+ * os_frames_ingest_u8: os_frames_ingest up to the byte L, without the division: gray [N][out_size][out_size] uint8 (its errors and
+ * limits are os_frames_ingest's).  os_frames_ingest's result is float(gray) / 255.
+ * os_frames_augment: gray [N][S][S] uint8 -> out [N][S][S] float32 in [0, 1], one launch, one workgroup per image, no allocation,
+ * no copy, no synchronise.  params [N][20] float64 on the device, integers stored as exact doubles:
+ *   [0:6]   a0..a5, the affine matrix that PIL's Image.rotate builds and hands to transform(AFFINE) (the matrix, not the angle:
+ *           rotate rounds cos and sin in Python); applied in Pillow's 16.16 fixed point
+ *   [6:14]  c0..c7, PIL's PERSPECTIVE data; applied in float64 with IEEE division, as Pillow does
+ *   [14]    flags: 1 rotate, 2 vertical flip, 4 horizontal flip, 8 perspective, 16 crop and resize back to S x S (a stage without
+ *           its flag is the identity and its fields are not read)
+ *   [15:19] crop top, left, height, width;  [19] 0
+ * The result is ToTensor(resized_crop(perspective(hflip(vflip(rotate(gray)))))).  S <= 256 (the image, its crop and the crop's
+ * coefficient tables live in one workgroup's LDS): beyond that -4 with the limit in os_last_error.  N < 1, S < 1, null or
+ * misaligned pointers: -2.  The records live on the device and the call reads nothing back, so it cannot reject a record: the kernel
+ * CLAMPS a crop into the image (top, left to [0, S - 1], height to [1, S - top], width to [1, S - left]) and reports nothing;
+ * optistate_amd.augment builds valid records. */
+int os_frames_ingest_u8(os_ctx *ctx, int32_t N, const uint8_t *frames, int32_t H, int32_t W, int32_t C, int32_t out_size,
+                        uint8_t *gray /* [N][out_size][out_size] */, void *stream);
+int os_frames_augment(os_ctx *ctx, int32_t N, const uint8_t *gray /* [N][S][S] */, int32_t S, const double *params /* [N][20] */,
+                      float *out /* [N][S][S] */, void *stream);
+
 /* Decoder half of the same class (transformer/transformer_model.py:137-175: forward_decoder, forward_loss, unpatchify).
  * `dec` carries img_size, patch_size, in_chans, embed_dim = decoder_embed_dim, depth = decoder_depth, num_heads =
  * decoder_num_heads, mlp_hidden; latent_dim is the encoder's embed_dim.  With Dd = decoder_embed_dim, L = 1 + (img/patch)^2 and

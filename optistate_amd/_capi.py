@@ -42,7 +42,7 @@ EXPORTS = [
     "os_gru_get_stack", "os_fused_set_tile", "os_stack_check", "os_kf_step_mpc",
     "os_vit_decoder_param_count", "os_vit_load_decoder", "os_vit_decode", "os_vit_recon_loss",
     "os_vit_train_ws_floats", "os_vit_forward_train", "os_vit_backward", "os_vit_adamw_step",
-    "os_frames_ingest", "os_vit_encode_frames", "os_frames_plan_info",
+    "os_frames_ingest", "os_vit_encode_frames", "os_frames_plan_info", "os_frames_ingest_u8", "os_frames_augment",
 ]
 
 
@@ -156,7 +156,9 @@ def load():
     lib.os_frames_ingest.argtypes = [vp, i32, vp, i32, i32, i32, i32, f32p, vp]
     lib.os_vit_encode_frames.argtypes = [vp, i32, vp, i32, i32, i32, f32p, vp]
     lib.os_frames_plan_info.argtypes = [vp, i32, i32, i32, i32, C.POINTER(C.c_int64)]
-    for n in ("os_frames_ingest", "os_vit_encode_frames", "os_frames_plan_info"):
+    lib.os_frames_ingest_u8.argtypes = [vp, i32, vp, i32, i32, i32, i32, vp, vp]
+    lib.os_frames_augment.argtypes = [vp, i32, vp, i32, vp, f32p, vp]
+    for n in ("os_frames_ingest", "os_vit_encode_frames", "os_frames_plan_info", "os_frames_ingest_u8", "os_frames_augment"):
         getattr(lib, n).restype = C.c_int
     lib.os_mpc_set_weights.argtypes = [vp, C.POINTER(C.c_double), C.c_double, C.c_double, C.c_double]
     lib.os_mpc_solve.argtypes = [vp, i32, f32p, f32p, f32p, vp, f32p, f32p, vp, vp, i32, vp]

@@ -20,8 +20,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "liboptistate_hip.so")
-SOURCES = ["capi.hip", "kf_kernels.hip", "kf_rows_kernel.hip", "kf_dense_rows.hip", "kf_step.hip", "gru_kernels.hip", "gru_bf16_kernels.hip", "gru_wide_kernel.hip", "fused_kernels.hip", "gru_train_kernels.hip", "vit_kernels.hip", "vit_decoder.hip", "vit_train.hip", "vit_optim.hip", "frames_kernels.hip", "mpc_kernels.hip", "mpc_quad.hip"]
-HEADERS = ["kf_device.hpp", "kf_dense_rows.hpp", "kf_args.hpp", "kf_rows_chain.inc", "gru_common.hpp", "gru_device.hpp", "launch.hpp", "vit_host.hpp", "mpc_common.hpp", os.path.join("..", "..", "include", "optistate_hip.h")]
+SOURCES = ["capi.hip", "kf_kernels.hip", "kf_rows_kernel.hip", "kf_dense_rows.hip", "kf_step.hip", "gru_kernels.hip", "gru_bf16_kernels.hip", "gru_wide_kernel.hip", "fused_kernels.hip", "gru_train_kernels.hip", "vit_kernels.hip", "vit_decoder.hip", "vit_train.hip", "vit_optim.hip", "frames_kernels.hip", "frames_augment.hip", "mpc_kernels.hip", "mpc_quad.hip"]
+HEADERS = ["kf_device.hpp", "kf_dense_rows.hpp", "kf_args.hpp", "kf_rows_chain.inc", "gru_common.hpp", "gru_device.hpp", "launch.hpp", "vit_host.hpp", "frames_common.hpp", "mpc_common.hpp", os.path.join("..", "..", "include", "optistate_hip.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wno-pass-failed"]
 # per-file additions (the reason is in the file's header)
@@ -29,11 +29,13 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wno-pass-faile
 # persistent kernels' outer loops and then SPILLS them -- a scratch reload where two v_mov would do (kf_mpc_rows_kernel at two wavefronts
 # per SIMD: 416 -> 176 B of scratch, B = 8,192 4.4e7 -> 5.1e7 steps/s; the drain phase of mpc_solve_quad_kernel: 28 -> 0 B)
 # vit_decoder.hip, vit_train.hip, vit_optim.hip, frames_kernels.hip: no packed-fp32 VALU forms (v_pk_fma_f32 and kin) in its kernels: scalar fp32 only
+# frames_augment.hip: its float64 coordinate arithmetic has to round where Pillow's does: no fused multiply-add anywhere in the file
 EXTRA_FLAGS = {"kf_rows_kernel.hip": ["-fno-slp-vectorize"], "mpc_quad.hip": ["-mllvm", "-disable-machine-licm"],
                "vit_decoder.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
                "vit_train.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
                "vit_optim.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
-               "frames_kernels.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
+               "frames_kernels.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+               "frames_augment.hip": ["-ffp-contract=off"]}
 
 
 def _all_flags():

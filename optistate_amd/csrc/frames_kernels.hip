@@ -29,8 +29,8 @@
 //           row (broadcast); the float stores of a wave are whole 256-byte runs at TW = 64.
 // The index splits idx -> (row, piece) and idx -> (column, row) divide by plan constants with a multiply-high (host-verified range).
 #include "vit_host.hpp"
+#include "frames_common.hpp"
 
-#include <math.h>
 #include <stdlib.h>
 #include <vector>
 
@@ -38,13 +38,13 @@ extern "C" int os_vit_encode(os_ctx *ctx, int32_t N, const float *images, float 
 
 namespace osfr {
 
-constexpr int PB = 22;            // Pillow's PRECISION_BITS = 32 - 8 - 2
 constexpr int NT = 256;
 constexpr int LDS_HARD = 64 * 1024;   // dynamic LDS without an attribute call; two workgroups per CU at the least
 
 struct IngestArgs {
     const uint8_t *frames;
-    float *out;
+    float *out;                                       // frames_ingest_kernel
+    uint8_t *out_u8;                                  // frames_ingest_u8_kernel: the byte L, before the division
     const int32_t *plan;
     size_t img_bytes, total_bytes;
     int N, S, row_bytes;
@@ -55,22 +55,8 @@ struct IngestArgs {
     int lds_raw, lds_mid;                             // byte offsets into the dynamic LDS block (the tables come first)
 };
 
-__device__ __forceinline__ uint32_t div_magic(uint32_t idx, int d, uint32_t m) { return d == 1 ? idx : __umulhi(idx, m); }
-
-// 16 bytes at p (16-byte aligned); bytes outside [lo, hi) are not read and come back as zero
-__device__ __forceinline__ uint4 load16(const uint8_t *p, const uint8_t *lo, const uint8_t *hi)
-{
-    const uintptr_t a = (uintptr_t)p, l = (uintptr_t)lo, h = (uintptr_t)hi;
-    if (a >= l && a + 16 <= h) return *(const uint4 *)p;
-    uint32_t w[4] = {0u, 0u, 0u, 0u};
-#pragma unroll
-    for (int b = 0; b < 16; b++)
-        if (a + b >= l && a + b < h) w[b >> 2] |= (uint32_t)p[b] << (8 * (b & 3));
-    return make_uint4(w[0], w[1], w[2], w[3]);
-}
-
-template <int C>
-__global__ __launch_bounds__(NT) void frames_ingest_kernel(const IngestArgs a)
+template <int C, bool U8>
+__device__ __forceinline__ void ingest_body(const IngestArgs &a)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     int32_t *cx = (int32_t *)lds;                        // [2 + ksx][TW]: rel, cnt, coefficients by tap
@@ -165,55 +151,32 @@ __global__ __launch_bounds__(NT) void frames_ingest_kernel(const IngestArgs a)
             L = (19595u * R + 38470u * G + 7471u * B + 32768u) >> 16;       // Pillow's L24 with its rounding
         } else
             L = min(acc[0] >> PB, 255u);
-        a.out[(size_t)n * a.S * a.S + (size_t)oy * a.S + ox] = __fdiv_rn((float)L, 255.0f);
+        const size_t o = (size_t)n * a.S * a.S + (size_t)oy * a.S + ox;
+        if (U8) a.out_u8[o] = (uint8_t)L;
+        else a.out[o] = __fdiv_rn((float)L, 255.0f);
     }
 }
+
+template <int C>
+__global__ __launch_bounds__(NT) void frames_ingest_kernel(const IngestArgs a) { ingest_body<C, false>(a); }
+
+// the same image as bytes: what the augmentation (frames_augment.hip) reads
+template <int C>
+__global__ __launch_bounds__(NT) void frames_ingest_u8_kernel(const IngestArgs a) { ingest_body<C, true>(a); }
 
 // ---- host: tables and plan ----
 
 struct Axis { int in, S, ks; std::vector<int> lo, cnt, coef; };       // coef [S][ks]
 
-// Pillow's precompute_coeffs + normalize_coeffs_8bpc for the triangle filter, operation for operation, in IEEE double without
-// contraction (the bits of these tables are the bits of the result)
+// the table of an axis: axis_entry (frames_common.hpp) for every output index
 static void build_axis(int in, int S, Axis &ax)
 {
-#pragma clang fp contract(off)
     ax.in = in; ax.S = S;
     ax.lo.assign(S, 0); ax.cnt.assign(S, 0);
-    if (in == S) {                       // pass-through: out = (2^21 + 2^22 p) >> 22 = p
-        ax.ks = 1;
-        ax.coef.assign(S, 1 << PB);
-        for (int xx = 0; xx < S; xx++) { ax.lo[xx] = xx; ax.cnt[xx] = 1; }
-        return;
-    }
     const double scale = (double)in / (double)S;
-    const double fs = scale < 1.0 ? 1.0 : scale;
-    const double support = fs;
-    const double ss = 1.0 / fs;
-    const int ks = 2 * (int)ceil(support) + 1;
-    ax.ks = ks;
-    ax.coef.assign((size_t)S * ks, 0);
-    std::vector<double> w(ks);
-    for (int xx = 0; xx < S; xx++) {
-        const double center = (xx + 0.5) * scale;
-        int xmin = (int)(center - support + 0.5);
-        if (xmin < 0) xmin = 0;
-        int xmax = (int)(center + support + 0.5);
-        if (xmax > in) xmax = in;
-        const int cnt = xmax - xmin;
-        double ww = 0.0;
-        for (int x = 0; x < cnt; x++) {
-            double v = (x + xmin - center + 0.5) * ss;
-            if (v < 0.0) v = -v;
-            w[x] = v < 1.0 ? 1.0 - v : 0.0;
-            ww += w[x];
-        }
-        for (int x = 0; x < cnt; x++) {
-            const double k = ww != 0.0 ? w[x] / ww : w[x];
-            ax.coef[(size_t)xx * ks + x] = (int)(0.5 + k * (double)(1 << PB));
-        }
-        ax.lo[xx] = xmin; ax.cnt[xx] = cnt;
-    }
+    ax.ks = in == S ? 1 : 2 * (int)ceil(scale < 1.0 ? 1.0 : scale) + 1;
+    ax.coef.assign((size_t)S * ax.ks, 0);
+    for (int xx = 0; xx < S; xx++) axis_entry(in, S, xx, ax.lo[xx], ax.cnt[xx], &ax.coef[(size_t)xx * ax.ks], 1);
 }
 
 struct Plan {
@@ -232,8 +195,6 @@ struct State {
     uint64_t clock;
     float *fbuf; size_t fbuf_floats;   // os_vit_encode_frames: the frames between the two halves
 };
-
-static uint32_t magic_of(int d) { return d <= 1 ? 0u : (uint32_t)((((uint64_t)1 << 32) + (uint64_t)d - 1) / (uint64_t)d); }
 
 struct Windows { int n, T; std::vector<int> w0, wn; int wn_max; };
 
@@ -394,16 +355,20 @@ static int check_geometry(os_ctx *ctx, const char *who, int N, const void *frame
     return 0;
 }
 
-static int ingest(os_ctx *ctx, int N, const uint8_t *frames, int H, int W, int C, int S, float *out, hipStream_t s)
+// out: float32 [N][S][S], or with u8 the bytes before the division
+static int ingest(os_ctx *ctx, int N, const uint8_t *frames, int H, int W, int C, int S, void *out, bool u8, hipStream_t s)
 {
     Plan *p = nullptr;
     if (int rc = plan_get(ctx, H, W, C, S, &p)) return rc;
     IngestArgs a = p->args;
     const uint64_t blocks = (uint64_t)N * a.ntx * a.nty;
     if (blocks > 0x7fffffffull) return os_fail(ctx, -4, "os_frames_ingest: more than 2^31 - 1 tiles in one call: split the batch");
-    a.frames = frames; a.out = out; a.N = N; a.total_bytes = (size_t)N * a.img_bytes;
-    const int slot = os_prof_begin(ctx, OS_PHASE_VIT_MISC, s, C == 3 ? "frames_ingest_kernel<3>" : "frames_ingest_kernel<1>");
-    if (C == 3) hipLaunchKernelGGL(frames_ingest_kernel<3>, dim3((unsigned)blocks), dim3(NT), p->lds_bytes, s, a);
+    a.frames = frames; a.out = u8 ? nullptr : (float *)out; a.out_u8 = u8 ? (uint8_t *)out : nullptr; a.N = N; a.total_bytes = (size_t)N * a.img_bytes;
+    const int slot = os_prof_begin(ctx, OS_PHASE_VIT_MISC, s, u8 ? (C == 3 ? "frames_ingest_u8_kernel<3>" : "frames_ingest_u8_kernel<1>")
+                                                                   : (C == 3 ? "frames_ingest_kernel<3>" : "frames_ingest_kernel<1>"));
+    if (u8 && C == 3) hipLaunchKernelGGL(frames_ingest_u8_kernel<3>, dim3((unsigned)blocks), dim3(NT), p->lds_bytes, s, a);
+    else if (u8) hipLaunchKernelGGL(frames_ingest_u8_kernel<1>, dim3((unsigned)blocks), dim3(NT), p->lds_bytes, s, a);
+    else if (C == 3) hipLaunchKernelGGL(frames_ingest_kernel<3>, dim3((unsigned)blocks), dim3(NT), p->lds_bytes, s, a);
     else hipLaunchKernelGGL(frames_ingest_kernel<1>, dim3((unsigned)blocks), dim3(NT), p->lds_bytes, s, a);
     os_prof_end(ctx, slot, s);
     OS_HIP(ctx, hipGetLastError());
@@ -431,7 +396,16 @@ int os_frames_ingest(os_ctx *ctx, int32_t N, const uint8_t *frames, int32_t H, i
     OS_CHECK_CTX(ctx);
     if (int rc = osfr::check_geometry(ctx, "os_frames_ingest", N, frames, H, W, C, out_size, out)) return rc;
     OS_HIP(ctx, hipSetDevice(ctx->device));
-    return osfr::ingest(ctx, N, frames, H, W, C, out_size, out, (hipStream_t)stream);
+    return osfr::ingest(ctx, N, frames, H, W, C, out_size, out, false, (hipStream_t)stream);
+}
+
+int os_frames_ingest_u8(os_ctx *ctx, int32_t N, const uint8_t *frames, int32_t H, int32_t W, int32_t C, int32_t out_size, uint8_t *gray,
+                        void *stream)
+{
+    OS_CHECK_CTX(ctx);
+    if (int rc = osfr::check_geometry(ctx, "os_frames_ingest_u8", N, frames, H, W, C, out_size, gray)) return rc;
+    OS_HIP(ctx, hipSetDevice(ctx->device));
+    return osfr::ingest(ctx, N, frames, H, W, C, out_size, gray, true, (hipStream_t)stream);
 }
 
 int os_vit_encode_frames(os_ctx *ctx, int32_t N, const uint8_t *frames, int32_t H, int32_t W, int32_t C, float *latent, void *stream)
@@ -445,7 +419,7 @@ int os_vit_encode_frames(os_ctx *ctx, int32_t N, const uint8_t *frames, int32_t 
     osfr::State *st = osfr::state_get(ctx);
     if (!st) return -13;
     if (os_ensure_scratch(ctx, &st->fbuf, &st->fbuf_floats, (size_t)N * S * S)) return -10;
-    if (int rc = osfr::ingest(ctx, N, frames, H, W, C, S, st->fbuf, (hipStream_t)stream)) return rc;
+    if (int rc = osfr::ingest(ctx, N, frames, H, W, C, S, st->fbuf, false, (hipStream_t)stream)) return rc;
     return os_vit_encode(ctx, N, st->fbuf, latent, stream);
 }
 

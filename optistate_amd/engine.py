@@ -238,6 +238,34 @@ class Engine:
                     "os_frames_ingest")
         return out
 
+    def ingest_frames_u8(self, frames, size=224):
+        """ingest_frames up to the byte before the division (os_frames_ingest_u8): uint8 (N, size, size), what augment_frames reads;
+        `.float() / 255` of it is ingest_frames' result."""
+        fr, N, H, W, Cn = self._frames_u8(frames)
+        out = torch.empty((N, size, size), dtype=torch.uint8, device=self.device)
+        self._check(self.lib.os_frames_ingest_u8(self._h, N, C.c_void_p(fr.data_ptr()), H, W, Cn, int(size), C.c_void_p(out.data_ptr()),
+                                                 self._stream()), "os_frames_ingest_u8")
+        return out
+
+    def augment_frames(self, gray_u8, params):
+        """The training transform's random augmentations and ToTensor (transformer/autoencoder_training.py:45-52) with explicit
+        per-image parameters, bit for bit as Pillow computes them (os_frames_augment): gray_u8 uint8 (N, S, S) on the device, S <= 256;
+        params float64 (N, 20) records (optistate_amd.augment; a numpy array is copied over) -> float32 (N, S, S) in [0, 1]."""
+        fr, N, H, W, Cn = self._frames_u8(gray_u8)
+        if Cn != 1 or H != W:
+            raise ValueError(f"optistate_amd: square gray images (N,S,S) expected, got {tuple(fr.shape)}")
+        if isinstance(params, np.ndarray):
+            params = torch.from_numpy(np.ascontiguousarray(params)).to(self.device)
+        if not torch.is_tensor(params) or params.dtype != torch.float64 or tuple(params.shape) != (N, 20):
+            raise TypeError(f"optistate_amd: float64 records of shape ({N}, 20) expected, got "
+                            f"{getattr(params, 'dtype', type(params))} {tuple(getattr(params, 'shape', ()))}")
+        if not params.is_cuda or not params.is_contiguous():
+            raise ValueError("optistate_amd: the records must be a contiguous device tensor (or a numpy array)")
+        out = torch.empty((N, H, W), dtype=torch.float32, device=self.device)
+        self._check(self.lib.os_frames_augment(self._h, N, C.c_void_p(fr.data_ptr()), H, C.c_void_p(params.data_ptr()), _ptr(out),
+                                               self._stream()), "os_frames_augment")
+        return out
+
     def frames_plan_info(self, H, W, channels, size=224):
         """The ingest plan of a geometry (os_frames_plan_info) as a dict, for reports."""
         info = (C.c_int64 * 8)()

@@ -230,10 +230,15 @@ class Transformer_Autoencoder(nn.Module):
         with eng.lock:                                     # load + encode as one unit: a context holds ONE auto-encoder
             return self._encode_locked(eng, x)
 
-    def preprocess(self, frames):
+    def preprocess(self, frames, augment=None):
         """uint8 frames (N,H,W,3) | (N,H,W,1) | (N,H,W) on the device (or a numpy array) -> (N,1,img_size,img_size) float32: the
-        reference's `transform(img).unsqueeze(0)` (gru/gru_test.py:49-53,122-124), batched, bit for bit (Engine.ingest_frames)."""
+        reference's `transform(img).unsqueeze(0)` (gru/gru_test.py:49-53,122-124), batched, bit for bit (Engine.ingest_frames).
+        augment: float64 (N,20) records (optistate_amd.augment.sample_params) -> the training transform of
+        transformer/autoencoder_training.py:42-53 instead, the random augmentations between Grayscale and ToTensor applied with these
+        parameters (Engine.ingest_frames_u8 + Engine.augment_frames); img_size <= 256."""
         eng = default_engine(frames.device.index or 0) if torch.is_tensor(frames) and frames.is_cuda else default_engine(0)
+        if augment is not None:
+            return eng.augment_frames(eng.ingest_frames_u8(frames, self.img_size), augment).unsqueeze(1)
         return eng.ingest_frames(frames, self.img_size).unsqueeze(1)
 
     def encode_frames(self, frames):
