@@ -328,6 +328,8 @@ int os_gru_backward_ws(os_ctx *ctx, const os_gru_dims *d, const float *w_flat, i
  * Flat weight layout (device floats): patch_embed.proj.weight [D][P*P], .bias [D], cls_token [D], pos_embed [L][D]; per block:
  * norm1.weight, norm1.bias, attn.qkv.weight [3D][D], attn.qkv.bias [3D], attn.proj.weight [D][D], attn.proj.bias, norm2.weight,
  * norm2.bias, mlp.fc1.weight [M][D], mlp.fc1.bias [M], mlp.fc2.weight [D][M], mlp.fc2.bias [D]; then norm.weight, norm.bias.
+ * os_vit_load: head dimension 32 or 64, any token count.  Where K and V of a whole head no longer fit a workgroup's LDS (from 316
+ * tokens on at head dimension 64, from 621 on at 32) the attention runs on the key-tiled kernel (vit_attn_tiled.hip).
  * os_vit_encode: images [N][img][img] float in [0,1] (gru/gru_test.py:49-53) -> latent [N][D] = sigmoid(LN(cls token)). */
 typedef struct os_vit_dims {
     int32_t img_size, patch_size, in_chans, embed_dim, depth, num_heads, mlp_hidden;
@@ -405,8 +407,10 @@ int os_vit_recon_loss(os_ctx *ctx, int32_t N, const float *images, const float *
 
 /* Training step of the auto-encoder (transformer/autoencoder_training.py:103-114) for the pair loaded by os_vit_load and
  * os_vit_load_decoder (same image geometry, latent_dim = the encoder's embed_dim).  Supported: everything the two loads accept
- * with a head dimension of 32 and at most 224 tokens in encoder and decoder (their widths may differ); anything else returns -4
- * with a message (os_vit_train_ws_floats: 0).
+ * (head dimension 32 or 64 and any token count, per stack; widths and head counts of encoder and decoder may differ) with N *
+ * tokens * the widest row below 2^30; anything else returns -4 or -2 with a message (os_vit_train_ws_floats: 0).  A stack with
+ * 32-wide heads and at most 224 tokens runs the whole-head attention kernels, any other the key-tiled ones (vit_attn_tiled.hip),
+ * which keep the log-sum-exp of every (image, head, query) in the workspace; OS_VIT_ATT_TILED=1 sends every stack there.
  * os_vit_train_ws_floats: floats of the caller-owned workspace for N images.
  * os_vit_forward_train: encoder + decoder + loss as os_vit_encode / os_vit_decode compute them (unfused launches), keeping in ws
  * what the backward needs: per block its input, qkv, attention output, the residual stream behind the attention, the fc1

@@ -68,6 +68,7 @@ int os_create(const os_kf_config *cfg, os_ctx **out)
         e = getenv("OS_DW_FUSED"); c->tune_dw_fused = e ? atoi(e) : 1;
         e = getenv("OS_VIT_TAIL_SPLIT"); c->tune_vit_tail_split = e ? atoi(e) : 1;
         e = getenv("OS_VIT_ATT_DMA"); c->tune_vit_att_dma = e ? atoi(e) : 1;
+        e = getenv("OS_VIT_ATT_TILED"); c->tune_vit_att_tiled = e ? atoi(e) : 0;
         e = getenv("OS_VIT_MLP_BM"); c->tune_vit_mlp_bm = e ? atoi(e) : 64;
         e = getenv("OS_GRU_WIDE"); c->tune_gru_wide = e ? atoi(e) : 1; c->wide_attr_set = false;
         // frame ingest: LDS (KB) a tile should stay within; measured at 1,024 x 480 x 640 x 3 -> 224: 24 (16 x 32 tiles) 0.50 ms, 40 (16 x 64) 0.72, 64 (32 x 64) 1.08

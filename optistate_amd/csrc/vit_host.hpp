@@ -70,6 +70,13 @@ int os_vit_launch_gemm(os_ctx *ctx, int src, int epi, const osv::GemmArgs &g, hi
 // attention of every (image, head): QKV [N * L][3 dim] -> O [N * L][dim]
 int os_vit_launch_attention(os_ctx *ctx, os_vit_state *v, const osv::VitDims &d, int N, const float *QKV, const float *qkvb, float *O,
                             hipStream_t s);
+// the key-tiled kernels (vit_attn_tiled.hip): head dimension 32 or 64, any token count.  lse [N][heads][L]: the log-sum-exp of the
+// scaled logits in units of log 2 (null: not written); delta [N][heads][L]: scratch that the backward fills and reads.  dQKV in
+// the layout of QKV.
+int os_vit_launch_attention_tiled(os_ctx *ctx, const osv::VitDims &d, int N, const float *QKV, float *O, float *lse, hipStream_t s,
+                                  const char *name);
+int os_vit_launch_attention_tiled_bwd(os_ctx *ctx, const osv::VitDims &d, int N, const float *QKV, const float *O, const float *dO,
+                                      const float *lse, float *delta, float *dQKV, hipStream_t s);
 void os_vit_launch_cls_row(os_ctx *ctx, int N, int L, int D, const float *cls, const float *pos, float *X, hipStream_t s);
 void os_vit_launch_cls_head(os_ctx *ctx, int N, int L, int D, const float *X, const float *w, const float *b, float *latent, hipStream_t s);
 // the decoder's two ends (vit_decoder.hip): latent -> token matrix X; X behind the last block -> pred / recon / loss

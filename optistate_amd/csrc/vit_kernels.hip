@@ -1077,6 +1077,8 @@ int os_vit_launch_attention(os_ctx *ctx, os_vit_state *v, const VitDims &d, int 
     const int D = d.dim, L = ntok(d), hd = D / d.heads;
     const size_t alds = (size_t)2 * L * (hd + 1) * sizeof(float);
     const int ntl = (L + 31) / 32;
+    // K and V of a whole head no longer fit a workgroup's LDS (316 tokens at head dimension 64, 621 at 32): the key-tiled kernel
+    if (alds > 160 * 1024) return os_vit_launch_attention_tiled(ctx, d, N, big, Y, nullptr, s, "attention_tiled_fwd_kernel");
     const int slot = os_prof_begin(ctx, OS_PHASE_VIT_ATTN, s, (hd == 32 && ntl == 7) ? (ctx->tune_vit_att_dma ? "attention_mfma_dma_kernel<7>" : "attention_mfma_kernel<7>") : "attention_kernel");
     if (hd == 32 && ntl == 7) {              // the reference's shape: 197 tokens, head_dim 32 -> matrix cores
         const size_t mlds = (size_t)2 * L * 33 * sizeof(float);

@@ -8,7 +8,9 @@
 //
 // Backward, the kernels of this file:
 //   attention_bwd_kernel   one workgroup per (image, head): Q, K, V and dO of the head in LDS, wave w owns key tile w and keeps
-//                          its dK^T / dV^T tiles in accumulators across the query tiles (details at the kernel)
+//                          its dK^T / dV^T tiles in accumulators across the query tiles (details at the kernel): head dimension 32
+//                          and at most 224 tokens; every other stack runs the key-tiled kernels of vit_attn_tiled.hip, forward
+//                          (with softmax statistics kept in the workspace) and backward
 //   vit_dw_kernel          dW[n][k] = sum_m dY[m][n] X[m][k] and the bias gradient from the same pass, per M-slice partials
 //   reduce_parts_kernel    the partials summed in a fixed order: gradients are bit-reproducible
 //   ln_bwd_kernel          LayerNorm backward + the residual add of the incoming gradient; dgamma / dbeta as per-workgroup partials
@@ -483,9 +485,17 @@ BlockWs block_ws(const VitDims &d, size_t M)
     return o;
 }
 
-// the whole workspace: encoder blocks | encoder output X | latent | decoder blocks | decoder output X | pred
-struct TrainWs { size_t enc, lat, dec, pred, total; };
-TrainWs train_ws(const VitDims &e, const VitDims &dd, int N)
+// a stack whose attention runs on the key-tiled kernels (vit_attn_tiled.hip): whatever the whole-head backward cannot hold, and
+// every stack under OS_VIT_ATT_TILED=1
+bool att_tiled(const os_ctx *ctx, const VitDims &d)
+{
+    return d.dim / d.heads != 32 || ntok(d) > 224 || ctx->tune_vit_att_tiled;
+}
+
+// the whole workspace: encoder blocks | encoder output X | latent | decoder blocks | decoder output X | pred, then per block of a
+// stack on the tiled kernels its softmax statistics [N][heads][L] (encoder, decoder)
+struct TrainWs { size_t enc, lat, dec, pred, lse_enc, lse_dec, total; };
+TrainWs train_ws(const os_ctx *ctx, const VitDims &e, const VitDims &dd, int N)
 {
     const size_t M = (size_t)N * ntok(e);
     TrainWs o;
@@ -493,7 +503,9 @@ TrainWs train_ws(const VitDims &e, const VitDims &dd, int N)
     o.lat = o.enc + e.depth * block_ws(e, M).total + M * e.dim;
     o.dec = o.lat + (size_t)N * e.dim;
     o.pred = o.dec + dd.depth * block_ws(dd, M).total + M * dd.dim;
-    o.total = o.pred + (size_t)N * (ntok(dd) - 1) * dd.patch * dd.patch;
+    o.lse_enc = o.pred + (size_t)N * (ntok(dd) - 1) * dd.patch * dd.patch;
+    o.lse_dec = o.lse_enc + (att_tiled(ctx, e) ? e.depth * M * e.heads : 0);
+    o.total = o.lse_dec + (att_tiled(ctx, dd) ? dd.depth * M * dd.heads : 0);
     return o;
 }
 
@@ -511,9 +523,9 @@ int train_state(os_ctx *ctx, int N, os_vit_state **out)
     os_vit_state *v = (os_vit_state *)ctx->vit;
     if (!v || !v->w || !v->dec) return os_fail(ctx, -5, "os_vit training: call os_vit_load and os_vit_load_decoder first");
     const VitDims &e = v->d, &dd = v->dec->d;
-    if (e.dim / e.heads != 32 || dd.dim / dd.heads != 32 || ntok(e) > 224 || e.img != dd.img || e.patch != dd.patch ||
-        v->dec->latent_dim != e.dim)
-        return os_fail(ctx, -4, "os_vit training: needs head dimension 32 and at most 224 tokens in encoder and decoder (one image geometry)");
+    const int he = e.dim / e.heads, hdd = dd.dim / dd.heads;
+    if ((he != 32 && he != 64) || (hdd != 32 && hdd != 64) || e.img != dd.img || e.patch != dd.patch || v->dec->latent_dim != e.dim)
+        return os_fail(ctx, -4, "os_vit training: needs head dimension 32 or 64 in encoder and decoder and one image geometry");
     const size_t bigw = max2(max2(3 * e.dim, e.mlp), max2(3 * dd.dim, dd.mlp));
     if (N <= 0 || (uint64_t)N * ntok(e) * bigw * 4 >= (1ull << 32)) return os_fail(ctx, -2, "os_vit training: N must be positive and N * tokens * width below 2^30");
     *out = v;
@@ -539,6 +551,7 @@ struct Bwd {
     os_ctx *ctx; os_vit_state *v; hipStream_t s;
     size_t M;
     float *dX, *dT, *dBig, *Yn, *wt, *part;
+    float *delta;               // [N][heads][L] of the block in flight (stacks on the tiled attention kernels)
 };
 
 // grad[W | b] of a linear layer y = x W^T + b from dY [M][N] and X [M][K] (img: X are the image patches, dY in token rows)
@@ -591,8 +604,10 @@ void ln_grad(const Bwd &b, int D, const float *X, const float *dY, const float *
     reduce_parts(b.ctx, nblk, (size_t)2 * D, (size_t)2 * D, b.part, grad, b.s);
 }
 
-// forward of the blocks of d with the activations kept: ws at block 0's slices, w / wp as os_vit_run_blocks takes them
-int blocks_forward(os_ctx *ctx, os_vit_state *v, const VitDims &d, const float *w, const float *wp, float *ws, float *Y, int N, hipStream_t s)
+// forward of the blocks of d with the activations kept: ws at block 0's slices, w / wp as os_vit_run_blocks takes them; lse: block
+// 0's softmax statistics for a stack on the tiled attention kernels, else null
+int blocks_forward(os_ctx *ctx, os_vit_state *v, const VitDims &d, const float *w, const float *wp, float *ws, float *lse, float *Y, int N,
+                   hipStream_t s)
 {
     const int D = d.dim, Mh = d.mlp;
     const size_t M = (size_t)N * ntok(d);
@@ -606,7 +621,9 @@ int blocks_forward(os_ctx *ctx, os_vit_state *v, const VitDims &d, const float *
         g.A = Y; g.lda = D; g.N = 3 * D; g.K = D; g.Wp = wp; g.bias = w + o.qkvb; g.C = ws + k.qkv; g.R = nullptr; g.C2 = nullptr;
         if (int rc = os_vit_launch_gemm(ctx, 0, 0, g, s, "vit_gemm_kernel<+bias>")) return rc;
         wp += (size_t)3 * D * D;
-        if (int rc = os_vit_launch_attention(ctx, v, d, N, ws + k.qkv, w + o.qkvb, ws + k.ao, s)) return rc;
+        if (lse) {
+            if (int rc = os_vit_launch_attention_tiled(ctx, d, N, ws + k.qkv, ws + k.ao, lse + (size_t)blk * M * d.heads, s, "attention_tiled_fwd_kernel<lse>")) return rc;
+        } else if (int rc = os_vit_launch_attention(ctx, v, d, N, ws + k.qkv, w + o.qkvb, ws + k.ao, s)) return rc;
         g.A = ws + k.ao; g.N = D; g.Wp = wp; g.bias = w + o.projb; g.C = ws + k.xmid; g.R = xin;
         if (int rc = os_vit_launch_gemm(ctx, 0, 4, g, s, "vit_gemm_kernel<+bias,+residual to>")) return rc;
         wp += (size_t)D * D;
@@ -623,14 +640,15 @@ int blocks_forward(os_ctx *ctx, os_vit_state *v, const VitDims &d, const float *
 }
 
 // backward of the blocks of d, last to first: b.dX holds the gradient of the last block's output on entry and of block 0's input
-// on return.  w / ws / grad at block 0; wtr: the stack's resident transposed packs (per block qkv, proj, fc1, fc2) or null.
-int blocks_backward(const Bwd &b, const VitDims &d, const float *w, const float *wtr, const float *ws, float *grad, int N)
+// on return.  w / ws / grad at block 0; wtr: the stack's resident transposed packs (per block qkv, proj, fc1, fc2) or null; lse:
+// block 0's softmax statistics as blocks_forward left them (tiled attention kernels), or null (attention_bwd_kernel).
+int blocks_backward(const Bwd &b, const VitDims &d, const float *w, const float *wtr, const float *ws, const float *lse, float *grad, int N)
 {
     const int D = d.dim, Mh = d.mlp;
     const BlockOff o = block_off(d);
     const BlockWs k = block_ws(d, b.M);
     os_vit_state *v = b.v;
-    if (!v->att_bwd_attr_set) {
+    if (!lse && !v->att_bwd_attr_set) {
         OS_HIP(b.ctx, hipFuncSetAttribute((const void *)attention_bwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         v->att_bwd_attr_set = true;
     }
@@ -652,9 +670,14 @@ int blocks_backward(const Bwd &b, const VitDims &d, const float *w, const float 
         // x_mid = x_in + proj(attention(qkv(LN1(x_in))))
         weight_grad(b, D, D, b.dX, D, a + k.ao, nullptr, nullptr, gb + o.projw);
         if (int rc = input_grad(b, D, D, wb + o.projw, tp, b.dX, b.dT, nullptr)) return rc;
-        const int slot = os_prof_begin(b.ctx, OS_PHASE_VIT_ATTN, b.s, "attention_bwd_kernel");
-        hipLaunchKernelGGL(attention_bwd_kernel, dim3(N * d.heads), dim3(512), alds, b.s, L, D, d.heads, a + k.qkv, a + k.ao, b.dT, b.dBig);
-        os_prof_end(b.ctx, slot, b.s);
+        if (lse) {
+            if (int rc = os_vit_launch_attention_tiled_bwd(b.ctx, d, N, a + k.qkv, a + k.ao, b.dT, lse + (size_t)blk * b.M * d.heads, b.delta, b.dBig, b.s))
+                return rc;
+        } else {
+            const int slot = os_prof_begin(b.ctx, OS_PHASE_VIT_ATTN, b.s, "attention_bwd_kernel");
+            hipLaunchKernelGGL(attention_bwd_kernel, dim3(N * d.heads), dim3(512), alds, b.s, L, D, d.heads, a + k.qkv, a + k.ao, b.dT, b.dBig);
+            os_prof_end(b.ctx, slot, b.s);
+        }
         os_vit_launch_layernorm(b.ctx, b.M, D, a + k.xin, wb + o.ln1, wb + o.ln1 + D, b.Yn, b.s);
         weight_grad(b, 3 * D, D, b.dBig, 3 * D, b.Yn, nullptr, nullptr, gb + o.qkvw);
         if (int rc = input_grad(b, 3 * D, D, wb + o.qkvw, tq, b.dBig, b.dT, nullptr)) return rc;
@@ -672,7 +695,7 @@ size_t os_vit_train_ws_floats(os_ctx *ctx, int32_t N)
 {
     if (!ctx || ctx->magic != OS_MAGIC) return 0;
     os_vit_state *v;
-    return train_state(ctx, N, &v) ? 0 : train_ws(v->d, v->dec->d, N).total;
+    return train_state(ctx, N, &v) ? 0 : train_ws(ctx, v->d, v->dec->d, N).total;
 }
 
 int os_vit_forward_train(os_ctx *ctx, int32_t N, const float *images, float *ws, float *pred, float *loss, void *stream)
@@ -689,7 +712,7 @@ int os_vit_forward_train(os_ctx *ctx, int32_t N, const float *images, float *ws,
     const size_t M = (size_t)N * L;
     if (os_ensure_scratch(ctx, &v->buf, &v->buf_floats, M * max2(D, Dd))) return -10;
     float *Y = v->buf;
-    const TrainWs t = train_ws(e, dd, N);
+    const TrainWs t = train_ws(ctx, e, dd, N);
     // encoder: patch embedding + position table, cls rows, blocks, sigmoid(LN(cls row))
     const float *w = v->w, *patch_b = w + (size_t)D * PP, *cls = patch_b + D, *pos = cls + D;
     w = pos + (size_t)L * D;
@@ -698,16 +721,16 @@ int os_vit_forward_train(os_ctx *ctx, int32_t N, const float *images, float *ws,
     g.M = (size_t)N * (L - 1); g.N = D; g.K = PP; g.Wp = v->wp; g.bias = patch_b; g.C = ws + t.enc; g.R = nullptr; g.C2 = nullptr;
     if (int rc = os_vit_launch_gemm(ctx, 1, 3, g, s, "vit_gemm_kernel<patch,+pos>")) return rc;
     os_vit_launch_cls_row(ctx, N, L, D, cls, pos, ws + t.enc, s);
-    if (int rc = blocks_forward(ctx, v, e, w, v->wp + (size_t)D * PP, ws + t.enc, Y, N, s)) return rc;
+    if (int rc = blocks_forward(ctx, v, e, w, v->wp + (size_t)D * PP, ws + t.enc, att_tiled(ctx, e) ? ws + t.lse_enc : nullptr, Y, N, s)) return rc;
     w += e.depth * block_off(e).total;
     os_vit_launch_cls_head(ctx, N, L, D, ws + t.enc + e.depth * block_ws(e, M).total, w, w + D, ws + t.lat, s);
     // decoder: token matrix, blocks, decoder_norm + decoder_pred + loss
     if (int rc = os_vit_dec_seed(ctx, q, N, ws + t.lat, ws + t.dec, s)) return rc;
     w = q->w + (size_t)Dd * D + 2 * Dd + (size_t)L * Dd;
-    if (int rc = blocks_forward(ctx, v, dd, w, q->wp, ws + t.dec, Y, N, s)) return rc;
+    if (int rc = blocks_forward(ctx, v, dd, w, q->wp, ws + t.dec, att_tiled(ctx, dd) ? ws + t.lse_dec : nullptr, Y, N, s)) return rc;
     w += dd.depth * block_off(dd).total;
     if (int rc = os_vit_dec_tail(ctx, q, N, w, ws + t.dec + dd.depth * block_ws(dd, M).total, images, ws + t.pred, nullptr, loss, s)) return rc;
-    if (pred) OS_HIP(ctx, hipMemcpyAsync(pred, ws + t.pred, (t.total - t.pred) * sizeof(float), hipMemcpyDeviceToDevice, s));
+    if (pred) OS_HIP(ctx, hipMemcpyAsync(pred, ws + t.pred, (t.lse_enc - t.pred) * sizeof(float), hipMemcpyDeviceToDevice, s));
     return 0;
 }
 
@@ -724,14 +747,15 @@ int os_vit_backward(os_ctx *ctx, int32_t N, const float *images, const float *ws
     const VitDims &e = v->d, &dd = q->d;
     const int D = e.dim, Dd = dd.dim, L = ntok(e), PP = e.patch * e.patch, NP = dd.patch * dd.patch;
     const size_t M = (size_t)N * L, Dm = max2(D, Dd), bigw = max2(max2(3 * D, e.mlp), max2(3 * Dd, dd.mlp));
-    const TrainWs t = train_ws(e, dd, N);
+    const TrainWs t = train_ws(ctx, e, dd, N);
     // scratch: dX | dT | Yn [M][Dm], dBig [M][bigw], dpred [M][NP] (token rows), the transposed pack of one matrix, the partials of
-    // one reduction, dlatent
+    // one reduction, dlatent, delta = rowsum(dO o O) of one block's attention (stacks on the tiled kernels)
     const size_t wt_floats = max2(max2((size_t)NP * Dd, max2(3 * (size_t)D * D, (size_t)e.mlp * D)), max2(3 * (size_t)Dd * Dd, (size_t)dd.mlp * Dd));
     const int slices = (int)((M + rows_per_slice(M) - 1) / rows_per_slice(M));
     const size_t nk = max2(max2((size_t)D * PP + D, wt_floats + bigw), (size_t)NP * Dd + NP);
     const size_t part_floats = max2(max2((size_t)slices * nk, ((M + LNB_ROWS - 1) / LNB_ROWS) * 2 * Dm), (size_t)N * 2 * Dm);
-    const size_t need = 3 * M * Dm + M * bigw + M * NP + wt_floats + part_floats + (size_t)N * D;
+    const size_t delta_floats = M * max2(att_tiled(ctx, e) ? e.heads : 0, att_tiled(ctx, dd) ? dd.heads : 0);
+    const size_t need = 3 * M * Dm + M * bigw + M * NP + wt_floats + part_floats + (size_t)N * D + delta_floats;
     if (os_ensure_scratch(ctx, &v->tbuf, &v->tbuf_floats, need)) return -10;
     Bwd b;
     b.ctx = ctx; b.v = v; b.s = s; b.M = M;
@@ -739,6 +763,7 @@ int os_vit_backward(os_ctx *ctx, int32_t N, const float *images, const float *ws
     float *dpred = b.dBig + M * bigw;
     b.wt = dpred + M * NP; b.part = b.wt + wt_floats;
     float *dlat = b.part + part_floats;
+    b.delta = dlat + (size_t)N * D;
     // ---- decoder ----
     const float *wd = q->w;
     const size_t o_be = (size_t)Dd * D, o_noise = o_be + Dd, o_dpos = o_noise + Dd, o_dblk = o_dpos + (size_t)L * Dd;
@@ -754,7 +779,7 @@ int os_vit_backward(os_ctx *ctx, int32_t N, const float *images, const float *ws
     const float *wtpred = wtd ? wtd + (size_t)dd.depth * (4 * (size_t)Dd * Dd + 2 * (size_t)dd.mlp * Dd) : nullptr;
     if (int rc = input_grad(b, NP, Dd, wd + o_pred, wtpred, dpred, b.dT, nullptr)) return rc;
     ln_grad(b, Dd, xd_out, b.dT, wd + o_dnorm, nullptr, b.dX, grad_dec + o_dnorm);
-    if (int rc = blocks_backward(b, dd, wd + o_dblk, wtd, ws + t.dec, grad_dec + o_dblk, N)) return rc;
+    if (int rc = blocks_backward(b, dd, wd + o_dblk, wtd, ws + t.dec, att_tiled(ctx, dd) ? ws + t.lse_dec : nullptr, grad_dec + o_dblk, N)) return rc;
     // the token matrix: decoder_embed (row 0 of every image), the noise token (the other rows), no gradient for the position table
     slot = os_prof_begin(ctx, OS_PHASE_TRAIN_MISC, s, "dec_seed_bwd_kernel");
     hipLaunchKernelGGL(dec_seed_bwd_kernel, dim3(N), dim3(256), 0, s, L, Dd, D, wd, b.dX, b.part, dlat);
@@ -775,7 +800,7 @@ int os_vit_backward(os_ctx *ctx, int32_t N, const float *images, const float *ws
     hipLaunchKernelGGL(enc_head_bwd_kernel, dim3((N + 3) / 4), dim3(256), 0, s, N, L, D, xe_out, we + o_norm, ws + t.lat, dlat, b.dX, b.part);
     os_prof_end(ctx, slot, s);
     reduce_parts(ctx, N, (size_t)2 * D, (size_t)2 * D, b.part, grad_enc + o_norm, s);
-    if (int rc = blocks_backward(b, e, we + o_blk, wte, ws + t.enc, grad_enc + o_blk, N)) return rc;
+    if (int rc = blocks_backward(b, e, we + o_blk, wte, ws + t.enc, att_tiled(ctx, e) ? ws + t.lse_enc : nullptr, grad_enc + o_blk, N)) return rc;
     reduce_parts(ctx, N, D, (size_t)L * D, b.dX, grad_enc + o_cls, s);
     weight_grad(b, D, PP, b.dX, D, nullptr, images, &e, grad_enc);
     fill(ctx, grad_enc + o_pos, (size_t)L * D, s);
