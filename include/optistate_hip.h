@@ -202,7 +202,10 @@ typedef struct os_gru_dims {
 size_t os_gru_param_count(const os_gru_dims *d);
 
 /* Replaces model.load_state_dict(...) (gru/gru_test.py:160): w_flat is a DEVICE float vector in the flat
- * layout above; the library re-packs it into MFMA fragment order in context scratch. */
+ * layout above; the library re-packs it into MFMA fragment order in context scratch.
+ * hidden_size: 32, 64, 128 (weights resident in registers) or 160, 192, 224, 256 (weights streamed from L2 every step:
+ * inference, training forward, backward sweep and weight gradients, all exact fp32, no atomics in the layer kernels); above
+ * 128 the input_size is at most 256 and os_gru_forward_windows is not available.  Other sizes return -4. */
 int os_gru_load(os_ctx *ctx, const os_gru_dims *d, const float *w_flat, void *stream);
 /* Every following os_gru_backward / os_gru_backward_ws on this context records `event` (a hipEvent_t; NULL switches it off) on
  * its stream right behind the weight-gradient kernel of GRU layer `layer`: from then on the gradients of layers layer..L-1 and

@@ -1510,7 +1510,10 @@ int os_gru_load_keyed(os_ctx *ctx, const os_gru_dims *d, const float *w_flat, ui
     OS_CHECK_CTX(ctx);
     if (!d || !w_flat) return os_fail(ctx, -2, "os_gru_load: null pointer");
     const int H = d->hidden_size;
-    if (H != 32 && H != 64 && H != 128) return os_fail(ctx, -4, "os_gru_load: hidden_size must be 32, 64 or 128");
+    if (H != 32 && H != 64 && H != 128 && !(H > 128 && H <= 256 && H % 32 == 0))
+        return os_fail(ctx, -4, "os_gru_load: hidden_size must be a multiple of 32, at most 256 (96 is not supported)");
+    if (H > 128 && d->input_size > 256)
+        return os_fail(ctx, -4, "os_gru_load: hidden sizes above 128 take an input_size of at most 256 (the streaming layer kernel's LDS tile)");
     if (d->input_size <= 0 || d->num_layers <= 0 || d->num_layers > 16 || d->num_classes <= 0 || d->num_classes > 256)
         return os_fail(ctx, -4, "os_gru_load: unsupported dimensions");
     OS_HIP(ctx, hipSetDevice(ctx->device));
@@ -1743,6 +1746,7 @@ extern "C" int os_stack_check(os_ctx *ctx, void *stream)
 // Launches gru_layer_kernel for one layer (shared by inference and the training forward).
 int os_gru_launch_layer(os_ctx *ctx, const LayerArgs &a, hipStream_t s)
 {
+    if (a.H > 128) return os_gru_stream_launch_layer(ctx, a, s);      // weights streamed, not resident (gru_stream_kernels.hip)
     if (ctx->gru_split_bf16) {               // opt-in reduced precision: H = 128 inference layers at large batches (gru_bf16_kernels.hip)
         bool done = false;
         const int rc = os_gru_try_layer_bf16(ctx, a, s, &done);

@@ -22,6 +22,7 @@
 #include "gru_common.hpp"
 #include "kf_device.hpp"   // buffer addressing helpers
 #include "gru_device.hpp"  // OSL_TS (development timestamps)
+#include "gru_train_args.hpp"  // SweepArgs, DwArgs (shared with gru_stream_kernels.hip)
 
 namespace ost {
 
@@ -195,25 +196,7 @@ __global__ void pack_T_all_kernel(const PackTAll a, int H3, float *zero, size_t 
     }
 }
 
-struct SweepArgs {
-    int B, T, K, H;
-    int need_dx;                 // write dx (layer > 0 or caller wants d(input))
-    const float *sv_r, *sv_z, *sv_n, *sv_g, *sv_h;   // [T][B][H]
-    const float *dy;             // [T][B][H] gradient w.r.t. this layer's outputs, or null
-    const float *dy_last;        // [B][H] gradient w.r.t. h_T only (top layer), or null
-    const float *wihT, *whhT;    // transposed-packed weights
-    float *dg4;                  // [T][B][4H]: da_r | da_z | da_n | da_n * r  (W_ih's products read sections 0-2, W_hh's 0, 1, 3)
-    float *dx;                   // [T][B][K]
-    // bwd_sweep_stack_kernel only (null otherwise): progress counters of the layer above (its dx is this layer's dy) and of this
-    // workgroup; a counter holds the number of steps published, T - t after step t
-    const uint32_t *flag_prev;
-    uint32_t *flag_mine;
-    int32_t *err = nullptr;      // the context's error word (launch.hpp): bit 0 = a bounded wait expired
-    int32_t *err_local = nullptr;    // its twin in device memory
-    uint32_t max_polls = 1u << 22;
-    int drop_from = -1;          // tests (OS_STACK_DBG_DROP): stop publishing once T - 1 - t reaches this count of steps done
-};
-
+// (SweepArgs: gru_train_args.hpp)
 // RB = 32-row blocks per workgroup (BM = 32*RB).  LDS: dh [BM][H+1] | dG [BM][4H+1] (sections da_r, da_z, da_n, da_n*r).
 // NW = wavefronts per workgroup.  The sweep is serial in T and a workgroup owns its rows, so at the training batch (8192
 // rows = one 32-row workgroup per CU) nothing else can hide a wave's stalls: eight waves (two per SIMD) split the gate
@@ -781,19 +764,7 @@ __global__ __launch_bounds__(512, 1) void bwd_sweep_stack_kernel(const SweepStac
 // gate chunk and up to 6 input chunks (96 accumulator registers), so dG is read once per wave and X once per gate chunk
 // (it stays in the 256 MiB Infinity Cache).  The T*B-long reduction is split over blockIdx.y; partial tiles are added
 // with fp32 atomics (two 128-B row segments per wave instruction).  The bias gradient rides along on the VALU.
-struct DwArgs {
-    int H3, K;                // gate units, input width
-    size_t r_begin, r_end;    // rows of dG to reduce (row r of dG pairs with row r - x_row_shift of X)
-    size_t x_row_shift;
-    size_t x_valid_from;      // dw2_kernel: rows below this pair with X = 0 (h_{-1}): they only count for the bias sum (multiple of 32)
-    int rows_per_slice;
-    const float *dG;          // [rows][ldg]: gate unit j sits in column j (+ nshift for the n gate, j >= 2 H3 / 3)
-    int ldg, nshift;          // the sweep's four-section array: ldg = 4H; nshift = 0 for W_ih (da_n), H for W_hh (da_n * r)
-    const float *X;           // [rows][K], or (B, T, K) batch_first when x_btf (row r = t*B + b lives at (b*T + t)*K)
-    int x_btf, B, T;
-    float *dW;                // [H3][K]
-    float *db;                // [H3] or null
-};
+// (DwArgs: gru_train_args.hpp)
 
 // Workgroup = 4 waves = 4 gate chunks (wave w owns chunk 4*blockIdx.x + w) over one slice of rows.  The X rows of a
 // 32-row tile are staged ONCE per workgroup through LDS (register-staged double buffering: the global loads of tile i+1
@@ -1541,6 +1512,8 @@ struct os_train_state {
     bool sweep_wide_attr_set;
     float *wT;    size_t wT_floats;      // transposed-packed weights
     float *lossp; size_t lossp_floats;   // loss_kernel: per-workgroup partial sums + ticket counter
+    float *dwp;   size_t dwp_floats;     // dw_stream_kernel (H > 128): per-slice partial images of one weight-gradient product
+    bool head_bwd_attr_set;              // hipFuncSetAttribute done for head_backward_kernel (its LDS tile passes 64 KB at H = 256)
     int B, T;
     // weight-gradient reductions of layer l run on a side stream underneath the backward sweep of layer l-1 (they only
     // depend on layer l's gate derivatives): non-blocking stream + events, created on first use
@@ -1577,7 +1550,7 @@ void os_train_destroy(os_ctx *ctx)
 {
     os_train_state *t = (os_train_state *)ctx->train;
     if (!t) return;
-    float *bufs[] = {t->act, t->seq, t->xs, t->dg, t->dxy, t->dhx, t->wT, t->lossp};
+    float *bufs[] = {t->act, t->seq, t->xs, t->dg, t->dxy, t->dhx, t->wT, t->lossp, t->dwp};
     for (float *b : bufs)
         if (b) (void)hipFree(b);
     if (t->side_ready) {
@@ -1788,7 +1761,11 @@ static int backward_impl(os_ctx *ctx, const os_gru_dims &d, const float *w_flat,
     float *dhT = ts->dxy + ndx * (size_t)T * B * Kmax;
     const float *hT = act + ((size_t)(L - 1) * 5 + 4) * tbh + (size_t)(T - 1) * B * H;   // sv_h of the top layer, t = T-1
     {
-        const size_t lds = (size_t)(64 * ((C + 31) / 32 * 32) + 64 * (H + 1)) * sizeof(float);
+        const size_t lds = (size_t)(64 * ((C + 31) / 32 * 32) + 64 * (H + 1)) * sizeof(float);      // 74 KB at H = 256, C <= 32; 131 KB at C = 256
+        if (lds > 64 * 1024 && !ts->head_bwd_attr_set) {
+            OS_HIP(ctx, hipFuncSetAttribute((const void *)head_backward_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+            ts->head_bwd_attr_set = true;
+        }
         const int slot = os_prof_begin(ctx, OS_PHASE_TRAIN_MISC, s, "head_backward_kernel");
         hipLaunchKernelGGL(head_backward_kernel, dim3((B + 63) / 64), dim3(512), lds, s, B, H, C, d.use_sigmoid, out, dout, hT,
                            fcw, dhT, grad_flat + fc_off, grad_flat + fc_off + (size_t)C * H);
@@ -1838,7 +1815,9 @@ static int backward_impl(os_ctx *ctx, const os_gru_dims &d, const float *w_flat,
         dim3 grid((B + BM - 1) / BM);
         int nw = (RB == 1 && ((a.need_dx ? (K + 31) / 32 : 0) + H / 32 >= 8 || (!a.need_dx && H / 32 >= 4))) ? 8 : 4;   // enough work items for eight waves
         if (ctx->tune_sweep_nw) nw = ctx->tune_sweep_nw == 8 && RB == 1 ? 8 : 4;
-        if (stacked && wide_bwd) {
+        if (H > 128) {                                         // weights streamed, dh in registers (gru_stream_kernels.hip)
+            if (const int rcs = os_gru_stream_launch_sweep(ctx, a, s)) return rcs;
+        } else if (stacked && wide_bwd) {
             if (l == L - 1) {                                  // four CUs per (layer, tile): bwd_sweep_wide_kernel
                 SweepWideArgs wa;
                 wa.n = L; wa.tiles = (B + 31) / 32;
@@ -1932,7 +1911,23 @@ static int backward_impl(os_ctx *ctx, const os_gru_dims &d, const float *w_flat,
         }
         const bool fuse_dw = ctx->tune_dw_fused != 0 && (K <= 128 || (wide && ctx->tune_dw_fused != 2)) && (K & 3) == 0 && (nchh == 4 || (nchh == 2 && ncx == 2)) && B % DW_TR == 0 &&
                              rps % DW_TR == 0 && T > 1 && (size_t)T * B * (K > H ? K : H) * 4 < ((size_t)1 << 31);
-        if (fuse_dw) {
+        if (H > 128) {
+            // dw_stream_kernel: run-time chunk counts, per-slice partial images added in slice order (no atomics); W_ih (+ b_ih) over
+            // every row, then W_hh (+ b_hh) with the rows of the first time step paired with h_{-1} = 0
+            ost::DwArgs d1;
+            d1.H3 = H3; d1.K = K; d1.r_begin = 0; d1.r_end = rows; d1.x_row_shift = 0; d1.x_valid_from = 0; d1.rows_per_slice = 0;
+            d1.dG = dg4; d1.ldg = 4 * H; d1.nshift = 0; d1.dW = gWih; d1.db = gbih; d1.B = B; d1.T = T;
+            if (l == 0) { d1.X = x; d1.x_btf = 1; }
+            else { d1.X = act + ((size_t)(l - 1) * 5 + 4) * tbh; d1.x_btf = 0; }
+            ost::DwArgs d2 = d1;
+            d2.K = H; d2.x_row_shift = (size_t)B; d2.x_valid_from = (size_t)B; d2.nshift = H; d2.X = base + 4 * tbh; d2.x_btf = 0;
+            d2.dW = gWhh; d2.db = gbhh;
+            const int dslot = os_prof_begin(ctx, OS_PHASE_TRAIN_DW, sw, "dw_stream_kernel");
+            if (const int rc1 = os_gru_stream_launch_dw(ctx, d1, &ts->dwp, &ts->dwp_floats, sw)) return rc1;
+            if (const int rc2 = os_gru_stream_launch_dw(ctx, d2, &ts->dwp, &ts->dwp_floats, sw)) return rc2;
+            os_prof_end(ctx, dslot, sw);
+            if (overlap) OS_HIP(ctx, hipEventRecord(ts->ev_dw[l], sw));
+        } else if (fuse_dw) {
             Dw3Args d;
             d.H3 = H3; d.Kx = K; d.H = H; d.rows = rows; d.rows_per_slice = rps; d.dG = dg4; d.ldg = 4 * H;
             d.B = B; d.T = T; d.Hp = base + 4 * tbh;
@@ -2028,7 +2023,9 @@ int os_gru_backward_ws(os_ctx *ctx, const os_gru_dims *d, const float *w_flat, i
     OS_CHECK_CTX(ctx);
     if (!d || B <= 0 || T <= 0) return os_fail(ctx, -2, "os_gru_backward_ws: bad argument");
     const int H = d->hidden_size;
-    if (H != 32 && H != 64 && H != 128) return os_fail(ctx, -4, "os_gru_backward_ws: hidden_size must be 32, 64 or 128");
+    if (H != 32 && H != 64 && H != 128 && !(H > 128 && H <= 256 && H % 32 == 0))
+        return os_fail(ctx, -4, "os_gru_backward_ws: hidden_size must be a multiple of 32, at most 256 (96 is not supported)");
+    if (H > 128 && d->input_size > 256) return os_fail(ctx, -4, "os_gru_backward_ws: hidden sizes above 128 take an input_size of at most 256");
     if (const int rcp = os_stack_pending(ctx, "os_gru_backward_ws")) return rcp;
     return backward_impl(ctx, *d, w_flat, ws, B, T, x, out, dout, grad_flat, dx, stream);
 }

@@ -101,6 +101,7 @@ struct os_ctx {
     double mass64, inertia64[3], gz64;
     float *mpc_scratch; size_t mpc_scratch_floats;
     bool fused_attr_set, sweep_attr_set, layer_attr_set, split_attr_set, ahead_attr_set, stage_attr_set, stack_attr_set;  // hipFuncSetAttribute(MaxDynamicSharedMemorySize) done on this device
+    bool stream_attr_set;                // ... for the weight-streaming kernels of hidden sizes above 128 (gru_stream_kernels.hip)
     void *vit;                           // os_vit_state (vit_kernels.hip), created by os_vit_load
     void *frames;                        // osfr::State (frames_kernels.hip): the frame-ingest plans per geometry, created on first use
     int tune_frames_lds_kb;              // OS_FRAMES_LDS_KB: LDS per workgroup that the ingest plan prefers when it picks a tile (the hard limit is 64)
@@ -189,6 +190,11 @@ bool os_gru_layer_takes_btf(os_ctx *ctx, int B, int T, int K, int H);   // gru_k
 int os_gru_head_launch(os_ctx *ctx, int B, const float *top, const float *fcw, float *out, hipStream_t s);
 bool os_gru_wide_eligible(os_ctx *ctx, int B, int T, int K0, int H, int n);                 // gru_wide_kernel.hip
 int os_gru_launch_wide(os_ctx *ctx, osg::WideArgs &a, bool save, hipStream_t s);
+// gru_stream_kernels.hip: hidden sizes 160 .. 256 (weights streamed from L2): layer, backward sweep, one weight-gradient product
+namespace ost { struct SweepArgs; struct DwArgs; }
+int os_gru_stream_launch_layer(os_ctx *ctx, const osg::LayerArgs &a, hipStream_t s);
+int os_gru_stream_launch_sweep(os_ctx *ctx, const ost::SweepArgs &a, hipStream_t s);
+int os_gru_stream_launch_dw(os_ctx *ctx, ost::DwArgs d, float **ws, size_t *ws_cap, hipStream_t s);
 void os_train_destroy(os_ctx *ctx);
 void os_step_destroy(os_ctx *ctx);
 void os_vit_destroy(os_ctx *ctx);
